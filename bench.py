@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: popgenWindows pi / dxy / Fst over 50 kb coordinate windows (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload northstar|c2|c3|c4|c5|popfreq|c2_w5k|tiny]
+    python bench.py --gpus N --steps K --warmup W [--workload northstar|c2|c3|c4|c5|popfreq|c2_w5k|tiny] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the line (headline, roofline of the dominant kernel, the warm-up pass's
+per-kernel times).  `--full` adds what is measured behind the headline: the CPU baseline, tiers T1 / T2 / VCF, the pipelined
+sub-batches, distMat's deferred table copy and, from 8 ranks on, `c5_share`.  `--dump-outputs DIR` writes what the last timed step
+returned to its caller as DIR/<name>.npy (float64; the inputs are the same seeded synthetic data set on every run).
 
 One process per GPU (RANK / LOCAL_RANK / WORLD_SIZE from the launcher).  A step is one pass of the whole per-window
 statistics path over the rank's resident synthetic data set: pack -> pairwise D/C -> population sums on the GPU, the float64
@@ -86,6 +91,8 @@ HBM_PEAK_GBS = 8000.0           # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 
 VALU_PEAK_GUIDE = 1024 * 2.4e9 / 2      # wave64 VALU instructions per second: 256 CUs x 4 SIMD-32, 2 cycles each, 2.4 GHz (guide)
 MFMA_FP4_PEAK_TFLOPS = 10000.0  # MX fp4 MFMA, dense (guide: ~10 PF; measured ceiling 9099 with 32x32x64)
 VALU_PAIRSITES_PEAK = 3.6e14    # 7 lane-ops per 32 pair-sites at 7.9e13 lane-ops/s
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this much array data in all (beyond it, a seeded sample of the rows)
+DUMP_SEED = 20261016
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -893,6 +900,33 @@ def t2_sample(eng, lay, wl, names, scaf_len, t0_table):
     return t2
 
 
+def step_outputs(tool, st, tab, gathered=None):
+    """What one timed step hands its caller, by name: popgenWindows the groupDistTable rows [window][column], distMat the
+    indPairTable [window][individual pair], popFreq / ABBA-BABA their statistics by name.  With several ranks: the rows of all
+    ranks that rank 0 gathered in the step (the dictionaries' columns in sorted order, sitesUsed not among them)."""
+    name = {"popgen": "groupDistTable", "distmat": "indPairTable"}.get(tool)
+    if gathered is not None:
+        if name is None and st:
+            return {k: gathered[:, i] for i, k in enumerate(sorted(k for k in st if k != "sitesUsed"))}
+        return {name or "table": gathered}
+    return {name: tab} if name else dict(st)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  Beyond `budget` bytes in all, the same seeded sample of
+    rows is kept of every array, and the sampled row numbers are written as out_dir/<name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.array(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in sorted(arrays.items()):
+        if total > budget and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (budget // 2) // total))       # (half the budget: the row numbers stay well inside it)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(n, script=None):
     """`python bench.py --gpus N` without a launcher: start the N ranks (one process per GPU, the environment a launcher would
     set), pass rank 0's JSON line through and wait for all of them.  No torch anywhere."""
@@ -945,6 +979,11 @@ def main():
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling: ONE data set of the workload's size, cut into window ranges by the drivers' multi-GPU plan "
                          "(genomics_general_amd.shardplan), every rank holds and computes only its range, the gather of the rows inside the time")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands behind the headline: CPU baseline, tiers T1 / T2 / VCF, pipelined sub-batches, distMat's "
+                         "deferred table copy, c5_share at N >= 8 (a plain run: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64; at most 64 MB in all)")
     ap.add_argument("--no-c5", action="store_true", help="at N >= 8: skip the c5_share measurement behind the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-tiers", action="store_true", help="skip the T1 (host blocks -> H2D -> kernels) and T2 (text -> CSV) samples")
@@ -1010,7 +1049,7 @@ def main():
     comm = dist.make_comm(eng, world)
     if world.size > 1 and isinstance(comm, dist.RcclComm):
         assert eng._comm_ranks() == world.size, "the RCCL communicator has %d ranks, expected %d" % (eng._comm_ranks(), world.size)
-    tiers = world.size == 1 and not args.no_tiers and wl["tool"] == "popgen" and not args.strong
+    tiers = args.full and world.size == 1 and not args.no_tiers and wl["tool"] == "popgen" and not args.strong
 
     def setup_data(wl, extra_rows_of=None):
         """Make the rank's data set resident and find its windows (untimed).  Weak scaling: rank r owns global sites
@@ -1129,13 +1168,14 @@ def main():
     comm.barrier()
     t0 = time.perf_counter()
     gather_s = 0.0
+    gathered = None
     for _ in range(args.steps):
         st, _tab = step()
         if world.size > 1:                                 # the drivers' one exchange per job: the finished rows meet on every rank
             g0 = time.perf_counter()
-            full = gather_rows(_tab, n_win, counts[:, 0])
+            gathered = gather_rows(_tab, n_win, counts[:, 0])
             gather_s += time.perf_counter() - g0
-            assert full.shape[0] == total_win
+            assert gathered.shape[0] == total_win
     eng.sync()
     my_elapsed = time.perf_counter() - t0
     comm.barrier()
@@ -1145,6 +1185,8 @@ def main():
     per_rank = comm.allgather(np.array([my_elapsed, elapsed])) if world.size > 1 else np.array([[my_elapsed, elapsed]])
     elapsed = float(np.max(per_rank[:, 1]))
     gather_ms = gather_s * 1e3 / args.steps if world.size > 1 else None
+    if args.dump_outputs and world.rank == 0:              # (before anything else runs a pass: the tables may share buffers)
+        dump_outputs(args.dump_outputs, step_outputs(wl["tool"], st, _tab, gathered))
 
     # ---- per-kernel timing of the timed region (HIP events on the engine's stream) ---------------------
     # dominant kernel = the kernel family with the most GPU time (chosen in the warm-up pass, timed live here)
@@ -1258,7 +1300,7 @@ def main():
         extra["result_table_copy"] = ("deferred (PG_BENCH_DEFER=1; no driver does this): the copy of pass k's table into page-locked memory runs on a "
                                       "stream of its own beside the kernels of pass k + 1 (pg_set_deferred_results); every table is complete at the "
                                       "synchronisation that ends the timed region")
-    elif wl["tool"] == "distmat" and world.size == 1:
+    elif wl["tool"] == "distmat" and world.size == 1 and args.full:
         # the experiment behind the headline: the same passes with the table's copy deferred
         eng.set_deferred_results(True)
         try:
@@ -1279,7 +1321,8 @@ def main():
     extra["kernel_ms_per_step_source"] = ("last warm-up step (all families bracketed by events); roofline.avg_launch_ms is from the timed region"
                                            if args.warmup >= 1 else "timed region")
     extra["whole_step_hbm_frac"] = round(n_hap * sites_per_step / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5)
-    if wl["tool"] == "popgen" and n_hap * sites_per_step >= (8 << 30) and not os.environ.get("PG_OVERLAP") and not args.no_tiers:
+    if (args.full and wl["tool"] == "popgen" and n_hap * sites_per_step >= (8 << 30) and not os.environ.get("PG_OVERLAP")
+            and not args.no_tiers):
         # side information: the same pass cut into >= 8 sub-batches whose pack kernel runs on a second stream beside the pair
         # kernels of the previous sub-batch (PG_OVERLAP=1).  Not the default: the kernels then share the GPU and a per-kernel
         # event bracket no longer times one kernel
@@ -1297,7 +1340,7 @@ def main():
 
     # ---- CPU baseline: the oracle's restatement of the reference's whole path on all host cores, bounded sample -------------
     cpu = None
-    if world.rank == 0 and world.size == 1 and not args.no_cpu_baseline:
+    if args.full and world.rank == 0 and world.size == 1 and not args.no_cpu_baseline:
         if wl["tool"] == "distmat":
             cpu = cpu_baseline_distmat(eng, lay, wl, lo, hi)
         else:
@@ -1321,7 +1364,8 @@ def main():
     # headline stays on ONE shape for N = 1, 2, 4, 8, so that a scaling curve compares like with like; this is the same pass at the
     # size config 5 asks for, a few steps, the gather inside the time
     c5_total = int(os.environ.get("PG_BENCH_C5_SITES", 3_000_000_000))        # (a smaller total lets a test run this section on one GPU)
-    if world.size >= 8 and (args.workload == "northstar" or "PG_BENCH_C5_SITES" in os.environ) and not args.strong and not args.no_c5:
+    if (args.full and world.size >= 8 and (args.workload == "northstar" or "PG_BENCH_C5_SITES" in os.environ) and not args.strong
+            and not args.no_c5):
         # (every rank decides together after each phase: a rank that fails -- out of memory on its 150 GB -- must not leave the others
         # waiting in an exchange it never enters)
         def all_ranks_ok(fn):

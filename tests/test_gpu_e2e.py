@@ -129,7 +129,7 @@ def test_bench_starts_its_own_ranks():
     # ranks fit the one GPU of the box); a share that cannot be set up is an `error` entry, never a hang
     env8 = dict(env, PG_BENCH_C5_SITES="2400000")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--workload", "tiny", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-tiers"], env=env8, capture_output=True, timeout=900)
+                        "--no-cpu-baseline", "--no-tiers", "--full"], env=env8, capture_output=True, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     d = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 8 and d["config"]["name"] == "tiny" and d["scaling"] == "weak"
@@ -144,6 +144,34 @@ def test_bench_starts_its_own_ranks():
         assert all(w > 0 for w in d["strong"]["windows_per_rank"]) and sum(d["strong"]["windows_per_rank"]) == 8      # 400 000 sites / 50 kb
         assert sum(d["strong"]["rank_bytes_share"]) == pytest.approx(1.0, abs=1e-3) and max(d["strong"]["rank_bytes_share"]) <= 1.0 / n + 0.13
         assert 8 * 2 / (d["ms_per_step"] * 2 / 1e3) == pytest.approx(d["value"], rel=1e-3)
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the line of the K timed steps and nothing measured
+    behind it; the table of the last timed step as DIR/groupDistTable.npy, the same table from a run of another step count"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    tables = []
+    for steps in (3, 5):
+        out = str(tmp_path / ("steps%d" % steps))
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", str(steps),
+                            "--warmup", "1", "--dump-outputs", out], env=env, capture_output=True, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout.decode()[-2000:]
+        d = json.loads(lines[0])
+        assert d["metric"] == "windows_per_sec" and d["unit"] == "windows/s" and d["higher_is_better"] is True
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        assert d["config"]["windows_per_gpu"] * steps / (d["ms_per_step"] * steps / 1e3) == pytest.approx(d["value"], rel=1e-3)
+        assert d["cpu_baseline"] is None and not {"t1", "t2", "vcf", "ms_per_step_pipelined_sub_batches"} & set(d)
+        assert os.listdir(out) == ["groupDistTable.npy"]
+        tab = np.load(os.path.join(out, "groupDistTable.npy"))
+        assert tab.dtype == np.float64 and tab.shape == (d["config"]["windows_per_gpu"], 16)         # 4 pi, 6 dxy, 6 Fst
+        tables.append(tab)
+    assert np.isfinite(tables[0]).any() and np.array_equal(tables[0], tables[1], equal_nan=True)
 
 
 @pytest.mark.parametrize("name,tool,size", [("holes_distmat_cat_nexus", "distMat.py", 2), ("holes_distmat_cat_nexus", "distMat.py", 3),

@@ -123,3 +123,32 @@ def test_roofline_traffic_comes_from_the_newest_profile_round():
     for wl in t["_source"]:
         assert os.path.exists(os.path.join(root, "profiles", rounds[-1], wl + "_kernel_stats.csv"))
         assert os.path.exists(os.path.join(root, "profiles", rounds[-1], wl + "_pmc_summary.json"))
+
+
+def test_bench_dump_outputs_names_the_arrays_and_keeps_to_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: what the timed step returned, by name, as float64 .npy files; an output beyond the budget keeps the
+    same seeded sample of rows on every run, and the sample's row numbers are written beside it"""
+    monkeypatch.syspath_prepend(ROOT)
+    monkeypatch.delenv("PG_BGZF_ZLIB", raising=False)           # (bench.py sets it for its own samples: not for the tests after this one)
+    import bench
+    tab = np.arange(12, dtype=np.float64).reshape(4, 3)
+    assert list(bench.step_outputs("popgen", None, tab)) == ["groupDistTable"]
+    assert list(bench.step_outputs("distmat", {"d": tab}, tab)) == ["indPairTable"]
+    st = {"D": np.ones(4), "fd": np.zeros(4), "sitesUsed": np.arange(4)}
+    assert sorted(bench.step_outputs("abba", st, tab)) == ["D", "fd", "sitesUsed"]
+    got = bench.step_outputs("abba", st, tab, gathered=np.arange(16.0).reshape(8, 2))
+    assert sorted(got) == ["D", "fd"] and np.array_equal(got["fd"], np.arange(1.0, 16.0, 2))
+    bench.dump_outputs(str(tmp_path / "a"), {"t": tab, "n": np.arange(4, dtype=np.int64)})
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["n.npy", "t.npy"]
+    back = np.load(str(tmp_path / "a" / "n.npy"))
+    assert back.dtype == np.float64 and np.array_equal(back, np.arange(4))
+    big = np.random.default_rng(1).random((1000, 64))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big}, budget=64 * 1000)
+    files = sorted(os.listdir(str(tmp_path / "b")))
+    assert files == ["big.npy", "big_rows.npy"]
+    size = sum(os.path.getsize(str(tmp_path / "b" / f)) for f in files)
+    assert size <= 64 * 1000 + 2 * 128                                     # (+ the two .npy headers)
+    rows = np.load(str(tmp_path / "b" / "big_rows.npy")).astype(np.int64)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "big.npy")), big[rows])
+    assert np.array_equal(rows, np.load(str(tmp_path / "c" / "big_rows.npy")))
