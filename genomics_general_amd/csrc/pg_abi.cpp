@@ -209,6 +209,12 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
         if (V.done) (void)hipEventDestroy(V.done);
         if (V.rows_ready) (void)hipEventDestroy(V.rows_ready);
     }
+    c->filt.sel_col.release(); c->filt.sel_ploidy.release(); c->filt.sel_popmask.release(); c->filt.coff.release(); c->filt.contigs.release(); c->filt.cflags.release();
+    for (int k = 0; k < 2; ++k) {
+        pg_ctx::FiltDev::Slot &F = c->filt.s[k];
+        F.flags.release(); F.out.release(); F.rlen.release(); F.roff.release(); F.pos.release(); F.status.release(); F.h_status.release(); F.df.release();
+        if (F.done) (void)hipEventDestroy(F.done);
+    }
     c->tok_pin.release();
     drop_events(c);
     c->gt.release();

@@ -4,6 +4,7 @@
 #include "pg_internal.h"
 #include "pg_inflate.h"
 #include "pg_vcf_core.h"
+#include "pg_filter_core.h"
 
 #include <utility>
 #include <vector>
@@ -184,6 +185,29 @@ struct pg_ctx {
         double kernel_ms = 0;                    // pg_vcf_dev_stats
         int64_t blocks = 0, host_blocks = 0;
     } vcf;
+    // .geno sites filtered on the device (pg_filter_dev.hip): the option set and, per text slot of the tokenizer, the lines' flags,
+    // positions, row sizes and places, the rows
+    struct FiltDev {
+        bool configured = false;
+        PgfConfig cfg;
+        DevBuf<int32_t> sel_col, sel_ploidy;
+        DevBuf<uint32_t> sel_popmask, coff;                 // coff: the contig names' offsets (n_contigs + 1)
+        DevBuf<uint8_t> contigs, cflags;
+        struct Slot {
+            DevBuf<uint8_t> flags, out;
+            DevBuf<uint32_t> rlen;
+            DevBuf<int64_t> roff, pos, status;             // status: [0] bits (1 a line needs the host, 2 the rows exceed `out`), [1] first such line, [2] bytes of the rows, [3] rows, [4] bytes of the rows as BGZF members
+            Deflate df;                                    // the rows deflated where they lie (pg_filter_dev_set_output)
+            HostPin<int64_t> h_status;
+            int64_t n_lines = 0;
+            hipEvent_t done = nullptr;
+            int state = 0;                                 // 0 idle, 1 text there, 2 kernels queued, 3 empty block
+            int64_t text_len = 0, out_cap = 0, first_line = 0;
+            bool no_final_newline = false;
+        } s[2];
+        bool bgzf_rows = false;
+        int64_t blocks = 0, host_blocks = 0;
+    } filt;
     int64_t tok_nl_fallbacks = 0;                          // deflated blocks whose line feeds were found by passes over the text after all
     HostPin<uint8_t> tok_pin;                              // two 4 MiB page-locked buffers per staging thread
     hipStream_t tok_st[PG_TOK_WORKERS] = {};               // one copy stream per staging thread

@@ -1,0 +1,556 @@
+// `.geno` sites filtered on the device: the filterGenotypes.py drop-in's route for the regular spelling of a line (fields split by
+// single tabs, the header's number of fields, ASCII).  The per-cell and per-site rules are csrc/pg_filter_core.h (the host route
+// pg_filter_text in pg_filter.cpp runs the same functions); this file is the division of the work over the chip and the host side of
+// the entry points.
+//
+//   k_filt_lines<0>  a wavefront per line: the line's tabs ranked by ballots into LDS, the contig looked up (a lane per listed name),
+//                    a lane per selected column classifies its cells, the sums reduced across the wave, siteTest; the line's flags,
+//                    its position (thinning) and its row's size
+//   k_filt_thin      (--thinDist only) a lane per pod walks its lines in order over the flags and positions (filterGenotypes.py:41-55)
+//   scan             the rows' places (k_vcf_scan, pg_vcf_dev.hip)
+//   k_filt_lines<1>  a wavefront per written line: the first two fields copied, the cells rendered, placed by a wave scan of their sizes
+// The text arrives in the tokenizer's text slot with its line feeds listed (pg_tok_text_submit / pg_tok_lines).  A line outside the
+// regular spelling, or one on which the reference raises, hands the BLOCK to the host route (pg_filter_dev_collect reports the line).
+#include "pg_ctx.h"
+#include "pg_filter_core.h"
+
+#include <algorithm>
+#include <cstring>
+
+int pg_tok_text_submit(pg_ctx *c, int slot, const char *text, int fd, int64_t file_offset, int64_t len);
+int pg_tok_lines(pg_ctx *c, int slot, int64_t *n_lines_out);
+int pg_tok_bgzf_submit(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                       const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                       int64_t text_len, int64_t line_len_hint);
+int pg_tok_crc_result(pg_ctx *c, int slot);
+int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
+                     const long long *status_d, long long *comp_total_d);
+void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
+
+namespace {
+
+#define PGF_ST_HOST 1ll
+#define PGF_ST_OVERFLOW 2ll
+
+// per-line flags of k_filt_lines<0>
+#define PGF_L_KEPT 1        // not skipped by --include / --exclude
+#define PGF_L_PASS 2        // siteTest passes (or --noTest)
+#define PGF_L_TEST_ERR 4    // siteTest raises
+#define PGF_L_ROW_ERR 8     // rendering the row raises
+
+#define PGF_MAX_CELL_IN 40  // cell bytes the device takes (PGF_MAXA alleles phased: 31)
+
+__device__ inline void raise_host(long long *status, long long line) {
+    atomicOr(reinterpret_cast<unsigned long long *>(status), (unsigned long long)PGF_ST_HOST);
+    atomicMin(status + 1, line);
+}
+
+__device__ inline int32_t wave_sum(int32_t x) {
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+    return x;
+}
+
+__device__ inline int wave_excl_scan(int x, int lane) {
+    int y = x;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(y, d, 64);
+        if (lane >= d) y += t;
+    }
+    return y - x;
+}
+
+struct FiltArgs {
+    const uint8_t *text;
+    const int64_t *nl;
+    int64_t n_lines;
+    const int32_t *sel_col, *sel_ploidy;
+    const uint32_t *sel_popmask, *coff;
+    const uint8_t *contigs, *cflags;
+    uint8_t *flags;
+    uint32_t *rlen;
+    int64_t *pos, *roff;
+    uint8_t *out;
+    long long *status;
+};
+
+// the cell of field c: [s, e) within the line, from the tab table
+__device__ inline void field_at(const uint32_t *tabs, int c, int n_cols, uint32_t n, uint32_t *s, uint32_t *e) {
+    *s = c ? tabs[c - 1] + 1 : 0;
+    *e = c < n_cols - 1 ? tabs[c] : n;
+}
+
+// the cells of the selected columns classified and summed: tot over the wave (the same on every lane), the populations' sums in LDS
+// (`pop`, n_pops records behind the tab table, added by LDS atomics: no per-lane array).  Returns false (on every lane) when some cell
+// needs the host
+__device__ bool line_sums(const FiltArgs &A, const PgfConfig &cfg, const uint8_t *line, const uint32_t *tabs, uint32_t n, int lane,
+                          PgfCounts *tot, PgfCounts *pop) {
+    int32_t *pw = reinterpret_cast<int32_t *>(pop);
+    for (int k = lane; k < cfg.n_pops * 6; k += 64) pw[k] = 0;
+    __syncthreads();
+    PgfCounts t = {};
+    bool bad = false;
+    for (int j = lane; j < cfg.n_sel; j += 64) {
+        uint32_t s, e;
+        field_at(tabs, A.sel_col[j], cfg.n_cols, n, &s, &e);
+        PgfGeno g;
+        if (e - s > PGF_MAX_CELL_IN || pgf_classify(line + s, (int)(e - s), cfg.in_fmt, A.sel_ploidy[j], cfg.force_ploidy, cfg.partial_to_missing, &g)) {
+            bad = true;
+            break;
+        }
+        pgf_add(g, &t);
+        const uint32_t mask = A.sel_popmask[j];
+        if (mask) {
+            PgfCounts one = {};
+            pgf_add(g, &one);
+            for (uint32_t m = mask; m; m &= m - 1) {
+                PgfCounts &q = pop[__builtin_ctz(m)];
+                for (int b = 0; b < 4; ++b)
+                    if (one.c[b]) atomicAdd(&q.c[b], one.c[b]);
+                if (one.calls) atomicAdd(&q.calls, one.calls);
+            }
+        }
+    }
+    __syncthreads();
+    if (__ballot(bad)) return false;
+    for (int b = 0; b < 4; ++b) tot->c[b] = wave_sum(t.c[b]);
+    tot->calls = wave_sum(t.calls);
+    tot->hets = wave_sum(t.hets);
+    return true;
+}
+
+// the line's tabs into LDS; false when the line is not of the regular spelling (the host's then)
+__device__ bool line_tabs(const uint8_t *line, uint32_t n, int n_cols, int lane, uint32_t *tabs) {
+    uint32_t ntab = 0;
+    bool irr = n == 0;
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t k = base + (uint32_t)lane;
+        const uint8_t b = k < n ? line[k] : (uint8_t)'x';
+        const bool tab = k < n && b == '\t';
+        const bool odd = k < n && (b == ' ' || b == '\v' || b == '\f' || b == '\r' || (b >= 0x1c && b <= 0x1f) || b >= 0x80);
+        const uint64_t m = __ballot(tab);
+        if (tab) {
+            const uint32_t idx = ntab + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (idx < (uint32_t)(n_cols - 1)) tabs[idx] = k;
+        }
+        ntab += (uint32_t)__popcll(m);
+        irr = irr || __ballot(odd) != 0;
+    }
+    if (irr || ntab != (uint32_t)(n_cols - 1)) return false;
+    __syncthreads();
+    bool empty = false;
+    for (int c = lane; c < n_cols; c += 64) {
+        uint32_t s, e;
+        field_at(tabs, c, n_cols, n, &s, &e);
+        empty = empty || e <= s;
+    }
+    return __ballot(empty) == 0;
+}
+
+// one row's size / its text
+template <int RENDER>
+__global__ __launch_bounds__(64) void k_filt_lines(FiltArgs A, PgfConfig cfg) {
+    extern __shared__ uint32_t tabs[];
+    const int lane = (int)threadIdx.x;
+    const int64_t i = blockIdx.x;
+    if (i >= A.n_lines) return;
+    if (RENDER && (A.rlen[i] == 0 || A.status[0] != 0)) return;   // (a raised status: the block is the host's, its rows are not written)
+    const int64_t ls = i ? A.nl[i - 1] + 1 : 0, le = A.nl[i];
+    const uint8_t *line = A.text + ls;
+    if (le - ls > 0x7fffffffll) {
+        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; raise_host(A.status, i); }
+        return;
+    }
+    const uint32_t n = (uint32_t)(le - ls);
+    if (!line_tabs(line, n, cfg.n_cols, lane, tabs)) {
+        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; raise_host(A.status, i); }
+        return;
+    }
+    const uint32_t f0e = tabs[0], f1s = tabs[0] + 1, f1e = cfg.n_cols > 2 ? tabs[1] : n;
+    if (!RENDER && cfg.contig_mode) {                              // filterGenotypes.py:37
+        bool in = false, ex = false;
+        for (int j = lane; j < cfg.n_contigs; j += 64) {
+            const uint32_t cs = A.coff[j], cl = A.coff[j + 1] - 1 - cs;
+            bool eq = cl == f0e;
+            for (uint32_t k = 0; eq && k < cl; ++k) eq = A.contigs[cs + k] == line[k];
+            in = in || (eq && (A.cflags[j] & 1));
+            ex = ex || (eq && (A.cflags[j] & 2));
+        }
+        in = __ballot(in) != 0;
+        ex = __ballot(ex) != 0;
+        if (((cfg.contig_mode & 1) && !in) || ((cfg.contig_mode & 2) && ex)) {
+            if (lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; }
+            return;
+        }
+    }
+    PgfCounts tot;
+    PgfCounts *pop = reinterpret_cast<PgfCounts *>(tabs + cfg.n_cols);
+    if (!line_sums(A, cfg, line, tabs, n, lane, &tot, pop)) {       // (a cell the reference raises on is worded by the host)
+        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; raise_host(A.status, i); }
+        return;
+    }
+    int order[4];
+    const int nA = pgf_order(tot.c, order);
+    if (!RENDER) {
+        uint8_t fl = PGF_L_KEPT;
+        bool host = false;
+        if (cfg.thin_dist) {
+            int64_t pos = 0;
+            host = pgf_parse_pos(line + f1s, (int)(f1e - f1s), &pos) != 0;
+            if (lane == 0) A.pos[i] = pos;
+        }
+        const int t = cfg.no_test ? 1 : pgf_site_test(cfg, tot, pop);
+        if (t == 1) fl |= PGF_L_PASS;
+        if (t < 0) fl |= PGF_L_TEST_ERR;
+        uint32_t len = 0;
+        if (t == 1) {                                              // the row's size: CHROM \t POS, a tab and the text of every cell, \n
+            bool err = false;
+            int sum = 0;
+            char cell[PGF_CELL_MAX];
+            for (int j = lane; j < cfg.n_sel; j += 64) {
+                uint32_t s, e;
+                field_at(tabs, A.sel_col[j], cfg.n_cols, n, &s, &e);
+                PgfGeno g;
+                pgf_classify(line + s, (int)(e - s), cfg.in_fmt, A.sel_ploidy[j], cfg.force_ploidy, cfg.partial_to_missing, &g);
+                const int L = pgf_render(cfg, g, order, nA, cell);
+                if (L < 0) err = true;
+                else sum += L + 1;
+            }
+            sum = wave_sum(sum);
+            if (__ballot(err)) fl |= PGF_L_ROW_ERR;
+            else len = f1e + (uint32_t)sum + 1;
+        }
+        // without thinning a raised siteTest or row stops here; with it, k_filt_thin decides whether the line gets that far
+        if (!cfg.thin_dist && (fl & (PGF_L_TEST_ERR | PGF_L_ROW_ERR))) host = true;
+        if (lane == 0) {
+            A.flags[i] = fl;
+            A.rlen[i] = (fl & PGF_L_ROW_ERR) ? 0 : len;
+            if (host) raise_host(A.status, i);
+        }
+        return;
+    }
+    // RENDER: CHROM \t POS as they stand, then the cells
+    uint8_t *o = A.out + A.roff[i];
+    for (uint32_t k = (uint32_t)lane; k < f1e; k += 64) o[k] = line[k];
+    uint32_t at = f1e;
+    char cell[PGF_CELL_MAX];
+    for (int base = 0; base < cfg.n_sel; base += 64) {
+        const int j = base + lane;
+        int L = 0;
+        if (j < cfg.n_sel) {
+            uint32_t s, e;
+            field_at(tabs, A.sel_col[j], cfg.n_cols, n, &s, &e);
+            PgfGeno g;
+            pgf_classify(line + s, (int)(e - s), cfg.in_fmt, A.sel_ploidy[j], cfg.force_ploidy, cfg.partial_to_missing, &g);
+            L = pgf_render(cfg, g, order, nA, cell);
+            if (L < 0) L = 0;                                      // (cannot happen: k_filt_lines<0> sent such rows to the host)
+        }
+        const int w = j < cfg.n_sel ? L + 1 : 0;
+        const int off = wave_excl_scan(w, lane);
+        if (j < cfg.n_sel) {
+            uint8_t *d = o + at + (uint32_t)off;
+            d[0] = '\t';
+            for (int k = 0; k < L; ++k) d[1 + k] = (uint8_t)cell[k];
+        }
+        at += (uint32_t)__shfl(off + w, 63, 64);
+    }
+    if (lane == 0) o[at] = '\n';
+}
+
+// --thinDist: a lane per pod of the block (the block starts at a pod boundary), its lines walked in order (filterGenotypes.py:32-55)
+__global__ __launch_bounds__(64) void k_filt_thin(FiltArgs A, PgfConfig cfg) {
+    const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const int64_t a = p * cfg.pod_size;
+    if (a >= A.n_lines) return;
+    const int64_t b = std::min<int64_t>(A.n_lines, a + cfg.pod_size);
+    bool have = false;
+    int64_t last_s = 0, last_n = 0, last_pos = 0;
+    for (int64_t i = a; i < b; ++i) {
+        const uint8_t fl = A.flags[i];
+        if (!(fl & PGF_L_KEPT)) continue;
+        const int64_t ls = i ? A.nl[i - 1] + 1 : 0;
+        int64_t cn = 0;
+        while (A.text[ls + cn] != '\t') ++cn;                     // (k_filt_lines<0> checked the tabs of a kept line)
+        bool same = have && cn == last_n;
+        for (int64_t k = 0; same && k < cn; ++k) same = A.text[ls + k] == A.text[last_s + k];
+        if (!same) { last_s = ls; last_n = cn; have = true; }
+        const bool keep = pgf_thin_keep(same, A.pos[i], &last_pos, cfg.thin_dist);
+        if (keep && (fl & PGF_L_TEST_ERR)) { raise_host(A.status, i); return; }
+        const bool pass = keep && (fl & PGF_L_PASS);
+        if (pass && (fl & PGF_L_ROW_ERR)) { raise_host(A.status, i); return; }
+        if (pass) last_pos = A.pos[i];
+        else A.rlen[i] = 0;
+    }
+}
+
+int check_slot(pg_ctx *c, int slot, const char *who) {
+    if (!c || slot < 0 || slot > 1) return pg_fail(PG_ERR_ARG, "%s: bad context or slot", who);
+    if (!c->filt.configured) return pg_fail(PG_ERR_STATE, "%s: pg_filter_dev_config must be called first", who);
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_filter_dev_config(pg_ctx *c, const pg_filter_cfg *cfg, const int32_t *sel_col, const int32_t *sel_ploidy,
+                                    const uint32_t *sel_popmask, const char *contigs, int n_contig_bytes, const uint8_t *contig_flags,
+                                    int *taken_out) {
+    if (!c || !cfg || !taken_out || n_contig_bytes < 0 || cfg->n_sel < 0 || cfg->n_pops < 0 || cfg->n_contigs < 0 ||
+        (cfg->n_sel && (!sel_col || !sel_ploidy || !sel_popmask)) || (cfg->n_contigs && (!contigs || !contig_flags)) ||
+        (cfg->thin_dist && cfg->pod_size < 1))
+        return pg_fail(PG_ERR_ARG, "pg_filter_dev_config: bad argument");
+    *taken_out = 0;
+    pg_ctx::FiltDev &D = c->filt;
+    D.configured = false;
+    // the tab table of a line lives in LDS (4 bytes per field, one wavefront per block); at most PGF_MAXPOP populations
+    if (cfg->n_cols < 2 || (size_t)cfg->n_cols * 4 + (size_t)cfg->n_pops * sizeof(PgfCounts) > 60 * 1024 || cfg->n_pops > PGF_MAXPOP) return PG_OK;
+    for (int j = 0; j < cfg->n_sel; ++j)
+        if (sel_col[j] < 0 || sel_col[j] >= cfg->n_cols || sel_ploidy[j] > PGF_MAXA) return PG_OK;
+    std::vector<uint32_t> coff{0};
+    for (int k = 0; k < cfg->n_contigs; ++k) {
+        const void *z = (int)coff.back() < n_contig_bytes ? memchr(contigs + coff.back(), 0, (size_t)(n_contig_bytes - (int)coff.back())) : nullptr;
+        if (!z) return pg_fail(PG_ERR_ARG, "pg_filter_dev_config: contig list shorter than n_contigs");
+        coff.push_back((uint32_t)(static_cast<const char *>(z) - contigs) + 1);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream_up));
+    const size_t ns = (size_t)std::max(cfg->n_sel, 1), nc = (size_t)std::max(cfg->n_contigs, 1);
+    int rc;
+    if ((rc = D.sel_col.ensure(ns)) != PG_OK || (rc = D.sel_ploidy.ensure(ns)) != PG_OK || (rc = D.sel_popmask.ensure(ns)) != PG_OK ||
+        (rc = D.coff.ensure(nc + 1)) != PG_OK || (rc = D.contigs.ensure((size_t)n_contig_bytes + 1)) != PG_OK || (rc = D.cflags.ensure(nc)) != PG_OK)
+        return rc;
+    if (cfg->n_sel) {
+        HIPCHK(hipMemcpy(D.sel_col.p, sel_col, (size_t)cfg->n_sel * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(D.sel_ploidy.p, sel_ploidy, (size_t)cfg->n_sel * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(D.sel_popmask.p, sel_popmask, (size_t)cfg->n_sel * 4, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(D.coff.p, coff.data(), coff.size() * 4, hipMemcpyHostToDevice));
+    if (n_contig_bytes) HIPCHK(hipMemcpy(D.contigs.p, contigs, (size_t)n_contig_bytes, hipMemcpyHostToDevice));
+    if (cfg->n_contigs) HIPCHK(hipMemcpy(D.cflags.p, contig_flags, (size_t)cfg->n_contigs, hipMemcpyHostToDevice));
+    D.cfg = *cfg;
+    D.configured = true;
+    *taken_out = 1;
+    return PG_OK;
+}
+
+// A block of whole lines (the last byte a line feed, else the block is the host's) into text slot `slot`; first_line: the block's first
+// data line of the file (with thinning a multiple of the pod size: a pod never spans two blocks)
+extern "C" int pg_filter_dev_submit(pg_ctx *c, int slot, const char *text, int64_t len, int64_t first_line) {
+    int rc = check_slot(c, slot, "pg_filter_dev_submit");
+    if (rc != PG_OK) return rc;
+    if ((!text && len) || len < 0 || first_line < 0) return pg_fail(PG_ERR_ARG, "pg_filter_dev_submit: no text");
+    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
+    if (c->filt.cfg.thin_dist && first_line % c->filt.cfg.pod_size)
+        return pg_fail(PG_ERR_ARG, "pg_filter_dev_submit: with --thinDist a block starts at a pod (line %lld)", (long long)first_line);
+    F.text_len = len;
+    F.first_line = first_line;
+    F.no_final_newline = len > 0 && text[len - 1] != '\n';
+    if ((rc = pg_tok_text_submit(c, slot, text, -1, 0, len)) != PG_OK) return rc;
+    F.state = len ? 1 : 3;
+    return PG_OK;
+}
+
+// The same for a block that is still bgzipped: the members cross PCIe deflated, k_inflate writes their text behind `head` in the slot
+// and lists its line feeds (pg_tok_bgzf_submit).  Not with thinning (the pods are cut in text).  Whether the text ends in a line feed is
+// read on the device once the line feeds are counted (the file's last block may not).
+extern "C" int pg_filter_dev_submit_bgzf(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                                         const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                                         int64_t text_len, int64_t first_line) {
+    int rc = check_slot(c, slot, "pg_filter_dev_submit_bgzf");
+    if (rc != PG_OK) return rc;
+    if (c->filt.cfg.thin_dist) return pg_fail(PG_ERR_ARG, "pg_filter_dev_submit_bgzf: not with --thinDist (pods are cut in text)");
+    if (first_line < 0 || text_len < 0) return pg_fail(PG_ERR_ARG, "pg_filter_dev_submit_bgzf: bad argument");
+    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
+    F.text_len = text_len;
+    F.first_line = first_line;
+    F.no_final_newline = false;                                   // (checked in pg_filter_dev_parse)
+    if ((rc = pg_tok_bgzf_submit(c, slot, comp, comp_len, in_off, in_len, out_len, crc, n_members, head, head_len, text_len, 1024)) != PG_OK)
+        return rc;
+    F.state = text_len ? 1 : 3;
+    return PG_OK;
+}
+
+// bgzf_members != 0: the rows of every block filtered from now on are also deflated on the device (k_deflate: BGZF members of 65 280
+// bytes of rows, no end-of-file member); pg_filter_dev_collect reports their bytes, pg_filter_dev_rows_bgzf fetches them
+extern "C" int pg_filter_dev_set_output(pg_ctx *c, int bgzf_members) {
+    if (!c) return pg_fail(PG_ERR_ARG, "pg_filter_dev_set_output: null context");
+    c->filt.bgzf_rows = bgzf_members != 0;
+    return PG_OK;
+}
+
+namespace {
+
+FiltArgs filt_args(pg_ctx *c, int slot) {
+    pg_ctx::FiltDev &D = c->filt;
+    pg_ctx::FiltDev::Slot &F = D.s[slot];
+    pg_ctx::TokSlot &T = c->tok[slot];
+    FiltArgs A;
+    A.text = T.tp;
+    A.nl = T.nl.p;
+    A.n_lines = F.n_lines;
+    A.sel_col = D.sel_col.p;
+    A.sel_ploidy = D.sel_ploidy.p;
+    A.sel_popmask = D.sel_popmask.p;
+    A.coff = D.coff.p;
+    A.contigs = D.contigs.p;
+    A.cflags = D.cflags.p;
+    A.flags = F.flags.p;
+    A.rlen = F.rlen.p;
+    A.pos = F.pos.p;
+    A.roff = F.roff.p;
+    A.out = F.out.p;
+    A.status = reinterpret_cast<long long *>(F.status.p);
+    return A;
+}
+
+size_t filt_lds(const PgfConfig &cfg) { return (size_t)cfg.n_cols * 4 + (size_t)cfg.n_pops * sizeof(PgfCounts); }
+
+// the rows' text (k_filt_lines<1>) and, for -o x.gz, their members (k_deflate), then the status back to the host
+int queue_render(pg_ctx *c, int slot, hipStream_t st) {
+    pg_ctx::FiltDev &D = c->filt;
+    pg_ctx::FiltDev::Slot &F = D.s[slot];
+    const FiltArgs A = filt_args(c, slot);
+    hipLaunchKernelGGL((k_filt_lines<1>), dim3((unsigned)F.n_lines), dim3(64), filt_lds(D.cfg), st, A, D.cfg);
+    HIPCHK(hipGetLastError());
+    if (D.bgzf_rows) {
+        int rc = pg_deflate_queue(c, st, F.df, F.out.p, A.status + 2, F.out_cap, A.status, A.status + 4);
+        if (rc != PG_OK) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(F.h_status.p, F.status.p, 40, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(F.done, st));
+    return PG_OK;
+}
+
+}  // namespace
+
+// Queues the kernels of the block in `slot` (waits for the number of its lines only)
+extern "C" int pg_filter_dev_parse(pg_ctx *c, int slot) {
+    int rc = check_slot(c, slot, "pg_filter_dev_parse");
+    if (rc != PG_OK) return rc;
+    pg_ctx::FiltDev &D = c->filt;
+    pg_ctx::FiltDev::Slot &F = D.s[slot];
+    if (F.state == 3) return PG_OK;
+    if (F.state != 1) return pg_fail(PG_ERR_STATE, "pg_filter_dev_parse: nothing submitted to slot %d", slot);
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream_up;
+    pg_ctx::TokSlot &T = c->tok[slot];
+    int64_t n_lines = 0;
+    if ((rc = pg_tok_lines(c, slot, &n_lines)) != PG_OK) { F.state = 0; return rc; }
+    F.n_lines = n_lines;
+    if ((rc = F.status.ensure(5)) != PG_OK || (rc = F.h_status.ensure(5)) != PG_OK) return rc;
+    if (!F.done) HIPCHK(hipEventCreateWithFlags(&F.done, hipEventDisableTiming));
+    if (T.deflated && n_lines > 0) {                              // does the inflated text end in a line feed (the file's last block may not)?
+        int64_t last = -1;
+        HIPCHK(hipMemcpyAsync(&last, T.nl.p + n_lines - 1, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        F.no_final_newline = last != F.text_len - 1;
+    }
+    // a block without a final line feed (the file's partial last line) is the host's; a '\r' in a line sends it there too (k_filt_lines)
+    const bool host_now = F.no_final_newline || n_lines == 0;
+    F.h_status.p[0] = host_now ? PGF_ST_HOST : 0;
+    F.h_status.p[1] = host_now ? 0 : 0x7fffffffffffffffll;
+    F.h_status.p[2] = F.h_status.p[3] = F.h_status.p[4] = 0;
+    if (host_now) {
+        F.state = 2;
+        HIPCHK(hipEventRecord(F.done, st));
+        return PG_OK;
+    }
+    if ((rc = F.flags.ensure_roomy((size_t)n_lines)) != PG_OK || (rc = F.rlen.ensure_roomy((size_t)n_lines)) != PG_OK ||
+        (rc = F.roff.ensure_roomy((size_t)n_lines)) != PG_OK || (rc = F.pos.ensure_roomy((size_t)n_lines)) != PG_OK)
+        return rc;
+    // rows: the text's own size for most formats; a larger total (str(tuple) cells, padded ploidies) grows the buffer in collect
+    F.out_cap = std::max<int64_t>(F.out_cap, T.len + n_lines * 16 + 4096);
+    if ((rc = F.out.ensure_roomy((size_t)F.out_cap + 64)) != PG_OK) return rc;
+    F.out_cap = (int64_t)F.out.cap - 64;                          // (k_deflate reads 32 bytes past the rows)
+    HIPCHK(hipMemcpyAsync(F.status.p, F.h_status.p, 40, hipMemcpyHostToDevice, st));
+    const FiltArgs A = filt_args(c, slot);
+    hipLaunchKernelGGL((k_filt_lines<0>), dim3((unsigned)n_lines), dim3(64), filt_lds(D.cfg), st, A, D.cfg);
+    if (D.cfg.thin_dist) {
+        const int64_t pods = (n_lines + D.cfg.pod_size - 1) / D.cfg.pod_size;
+        hipLaunchKernelGGL(k_filt_thin, dim3((unsigned)((pods + 63) / 64)), dim3(64), 0, st, A, D.cfg);
+    }
+    pg_rows_scan_queue(st, F.rlen.p, n_lines, F.roff.p, A.status, F.out_cap);
+    if ((rc = queue_render(c, slot, st)) != PG_OK) return rc;
+    F.state = 2;
+    ++D.blocks;
+    return PG_OK;
+}
+
+// Waits for the block's kernels.  *host_line_out < 0: the rows are ready (*rows_len_out bytes, *n_rows_out rows: pg_filter_dev_rows;
+// *bgzf_len_out bytes of members: pg_filter_dev_rows_bgzf); else the block goes to the host route -- line *host_line_out is the first
+// the device does not take.  Rows longer than the buffer (the scan knows their total) grow it and are rendered again.
+extern "C" int pg_filter_dev_collect(pg_ctx *c, int slot, int64_t *rows_len_out, int64_t *n_rows_out, int64_t *host_line_out,
+                                     int64_t *bgzf_len_out, int64_t *n_lines_out) {
+    int rc = check_slot(c, slot, "pg_filter_dev_collect");
+    if (rc != PG_OK) return rc;
+    if (!rows_len_out || !n_rows_out || !host_line_out) return pg_fail(PG_ERR_ARG, "pg_filter_dev_collect: null argument");
+    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
+    *rows_len_out = *n_rows_out = 0;
+    *host_line_out = -1;
+    if (bgzf_len_out) *bgzf_len_out = 0;
+    if (n_lines_out) *n_lines_out = 0;
+    if (F.state == 3) { F.state = 0; return PG_OK; }
+    if (F.state != 2) return pg_fail(PG_ERR_STATE, "pg_filter_dev_collect: nothing parsed in slot %d", slot);
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipEventSynchronize(F.done));
+    F.state = 0;
+    if (n_lines_out) *n_lines_out = F.n_lines;
+    if ((rc = pg_tok_crc_result(c, slot)) != PG_OK) return rc;
+    if (F.h_status.p[0] == PGF_ST_OVERFLOW) {                     // only the rows' room: grow it, render again
+        hipStream_t st = c->stream_up;
+        if ((rc = F.out.ensure_roomy((size_t)F.h_status.p[2] + 4096 + 64)) != PG_OK) return rc;
+        F.out_cap = (int64_t)F.out.cap - 64;
+        F.h_status.p[0] = 0;
+        F.h_status.p[4] = 0;
+        HIPCHK(hipMemcpyAsync(F.status.p, F.h_status.p, 40, hipMemcpyHostToDevice, st));
+        if ((rc = queue_render(c, slot, st)) != PG_OK) return rc;
+        HIPCHK(hipEventSynchronize(F.done));
+    }
+    if (F.h_status.p[0]) {
+        *host_line_out = (F.h_status.p[0] & PGF_ST_HOST) ? F.h_status.p[1] : 0;
+        ++c->filt.host_blocks;
+        return PG_OK;
+    }
+    *rows_len_out = F.h_status.p[2];
+    *n_rows_out = F.h_status.p[3];
+    if (bgzf_len_out && c->filt.bgzf_rows) *bgzf_len_out = F.h_status.p[4];
+    return PG_OK;
+}
+
+static int copy_back(pg_ctx *c, uint8_t *dst, const void *src, int64_t len) {
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
+    HIPCHK(hipMemcpyAsync(dst, src, (size_t)len, hipMemcpyDeviceToHost, c->tok_small));   // (beside the next block's kernels on stream_up)
+    HIPCHK(hipStreamSynchronize(c->tok_small));
+    return PG_OK;
+}
+
+extern "C" int pg_filter_dev_rows(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
+    int rc = check_slot(c, slot, "pg_filter_dev_rows");
+    if (rc != PG_OK) return rc;
+    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
+    if (len < 0 || (len && !dst) || (size_t)len > F.out.cap) return pg_fail(PG_ERR_ARG, "pg_filter_dev_rows: bad length");
+    return len ? copy_back(c, dst, F.out.p, len) : PG_OK;
+}
+
+extern "C" int pg_filter_dev_rows_bgzf(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
+    int rc = check_slot(c, slot, "pg_filter_dev_rows_bgzf");
+    if (rc != PG_OK) return rc;
+    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
+    if (len < 0 || (len && !dst) || (size_t)len > F.df.comp.cap) return pg_fail(PG_ERR_ARG, "pg_filter_dev_rows_bgzf: bad length");
+    return len ? copy_back(c, dst, F.df.comp.p, len) : PG_OK;
+}
+
+// the text of the collected block -> dst (a block that goes to the host route and whose text the host never had: BGZF)
+extern "C" int pg_filter_dev_text(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
+    int rc = check_slot(c, slot, "pg_filter_dev_text");
+    if (rc != PG_OK) return rc;
+    pg_ctx::TokSlot &T = c->tok[slot];
+    if (len < 0 || (len && !dst) || len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_filter_dev_text: bad length");
+    return len ? copy_back(c, dst, T.tp, len) : PG_OK;
+}
+
+extern "C" int pg_filter_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out) {
+    if (!c || !blocks_out || !host_blocks_out) return pg_fail(PG_ERR_ARG, "pg_filter_dev_stats: null argument");
+    *blocks_out = c->filt.blocks;
+    *host_blocks_out = c->filt.host_blocks;
+    return PG_OK;
+}

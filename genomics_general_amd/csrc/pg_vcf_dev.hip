@@ -420,6 +420,11 @@ extern "C" int pg_vcf_dev_submit_bgzf(pg_ctx *c, int slot, const uint8_t *comp, 
     return PG_OK;
 }
 
+// the rows' places of a block (k_vcf_scan), for the other per-line renderers (pg_filter_dev.hip): status [0] bits, [2] bytes, [3] rows
+void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap) {
+    hipLaunchKernelGGL(k_vcf_scan, dim3(1), dim3(1024), 0, st, rlen, n_lines, roff, status, out_cap);
+}
+
 // Queues the kernels of the block in `slot` (waits for the number of its lines only).
 extern "C" int pg_vcf_dev_parse(pg_ctx *c, int slot) {
     int rc = check_slot(c, slot, "pg_vcf_dev_parse");

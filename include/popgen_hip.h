@@ -559,6 +559,65 @@ int pg_comm_allgather_f64(pg_ctx *ctx, const double *send, double *recv, int64_t
 int pg_comm_barrier(pg_ctx *ctx);
 int pg_comm_destroy(pg_ctx *ctx);
 
+/* ---- `.geno` sites filtered (the filterGenotypes.py drop-in, genomics_general_amd/filtergeno.py) --------------------------------
+ * Replaces filterGenotypes.py:24-58 (analysisWrapper: include / exclude, thinning per pod, siteTest, the output row) with
+ * genomics.py:317-378 (Genotype), 465-575 (GenomeSite.asList / alleles / hets / nonMissing) and 742-799 (siteTest).  The per-cell and
+ * per-site rules are csrc/pg_filter_core.h.  The option set: */
+#define PG_FILTER_MAXPOP 32
+typedef struct pg_filter_cfg {
+    int32_t in_fmt, out_fmt, freq_order, force_ploidy, partial_to_missing, no_test;   /* -if 0 phased 1 diplo 2 alleles; -of 0 phased 1 diplo
+                                                                                      2 bases 3 alleles 4 randomAllele 5 coded 6 count */
+    int32_t n_sel, n_pops, n_cols, n_contigs, contig_mode;  /* n_cols: the header's fields; contig_mode: 1 --include given, 2 --exclude given */
+    int32_t min_calls, min_alleles, min_var, has_max_het, hwe, fixed, has_pop_calls, has_pop_alleles, has_nfd;
+    double max_alleles, max_het, min_freq, max_freq, nfd;    /* min_var / min_freq / max_freq 0: off */
+    int64_t thin_dist, pod_size;                             /* thin_dist 0: no thinning */
+    int32_t pop_calls_min[PG_FILTER_MAXPOP], pop_alleles_min[PG_FILTER_MAXPOP], pop_alleles_max[PG_FILTER_MAXPOP];
+    uint32_t pop_empty;                                      /* bit k: population k has no sample */
+    uint32_t pop_missing;                                    /* bit k: population k names a sample that is not selected (the
+                                                                reference raises KeyError where a line reaches its filters) */
+    int32_t universal_newlines;                              /* 1: a lone \r ends a line too (a file read in text mode); 0: stdin,
+                                                                where \r is whitespace inside the line */
+} pg_filter_cfg;
+/* The tables beside it: sel_col[n_sel] the header field of each selected sample, sel_ploidy[n_sel] (-1: none given), sel_popmask[n_sel]
+ * the populations (bits) a sample belongs to; contigs: n_contigs names, each ended by a 0 byte, contig_flags[n_contigs] 1 include 2 exclude.
+ *
+ * Host route, every spelling line.split() takes: text[0 .. len) holds data lines (universal newlines), the first of them data line
+ * first_line of the file (0-based, the pods count from there); the rows -> *rows_out (free with pg_filter_free).  A line on which the
+ * reference's worker raises: *err_line_out its index in the block, *err_code_out the PGF_E_* code (pg_filter_core.h), else -1 / 0. */
+int pg_filter_text(const pg_filter_cfg *cfg, const int32_t *sel_col, const int32_t *sel_ploidy, const uint32_t *sel_popmask,
+                   const char *contigs, int n_contig_bytes, const uint8_t *contig_flags, const char *text, int64_t len, int64_t first_line,
+                   int n_threads, char **rows_out, int64_t *rows_len_out, int64_t *n_rows_out, int64_t *err_line_out, int *err_code_out);
+void pg_filter_free(char *rows);
+/* Device route (csrc/pg_filter_dev.hip) for the regular spelling (fields split by single tabs, the header's field count, ASCII):
+ *   pg_filter_dev_config      the option set; *taken_out = 0 when the device does not take it (more than PG_FILTER_MAXPOP populations,
+ *                             a header too wide for the tab table in LDS)
+ *   pg_filter_dev_submit      a block of whole lines -> the tokenizer's text slot `slot` (0 / 1), its line feeds listed there; with
+ *                             thinning the block must hold whole pods (first_line: the block's first data line)
+ *   pg_filter_dev_submit_bgzf the same for a block still deflated (bgzip's members, pg_bgzf_walk's table; head: text in front of them):
+ *                             the members cross PCIe deflated and k_inflate writes their text into the slot (no thinning: pods
+ *                             cannot be cut in text the host never holds)
+ *   pg_filter_dev_parse       queues k_filt_lines<0>, k_filt_thin (thinning only), the rows' scan, k_filt_lines<1> (and k_deflate)
+ *   pg_filter_dev_collect     waits.  *host_line_out < 0: *rows_len_out bytes of rows (*n_rows_out) are ready for pg_filter_dev_rows
+ *                             (as *bgzf_len_out bytes of BGZF members for pg_filter_dev_rows_bgzf when pg_filter_dev_set_output(ctx, 1));
+ *                             rows longer than the buffer grow it and are rendered again; else line *host_line_out of the block is one
+ *                             the device does not take: the block goes to pg_filter_text (pg_filter_dev_text brings its text back).
+ *                             *n_lines_out: the block's line feeds
+ *   pg_filter_dev_stats       blocks filtered on the device / handed to the host so far */
+int pg_filter_dev_config(pg_ctx *ctx, const pg_filter_cfg *cfg, const int32_t *sel_col, const int32_t *sel_ploidy, const uint32_t *sel_popmask,
+                         const char *contigs, int n_contig_bytes, const uint8_t *contig_flags, int *taken_out);
+int pg_filter_dev_submit(pg_ctx *ctx, int slot, const char *text, int64_t len, int64_t first_line);
+int pg_filter_dev_submit_bgzf(pg_ctx *ctx, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                              const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                              int64_t text_len, int64_t first_line);
+int pg_filter_dev_set_output(pg_ctx *ctx, int bgzf_members);
+int pg_filter_dev_parse(pg_ctx *ctx, int slot);
+int pg_filter_dev_collect(pg_ctx *ctx, int slot, int64_t *rows_len_out, int64_t *n_rows_out, int64_t *host_line_out, int64_t *bgzf_len_out,
+                          int64_t *n_lines_out);
+int pg_filter_dev_rows(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
+int pg_filter_dev_rows_bgzf(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
+int pg_filter_dev_text(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
+int pg_filter_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
+
 #ifdef __cplusplus
 }
 #endif
