@@ -35,11 +35,11 @@ enum {
     PGF_E_PLOIDY = 2,      // ploidy mismatch without --forcePloidy (Genotype.__init__)
     PGF_E_DIPLO_IN = 3,    // -if diplo: not one of DIPLOTYPES (haplo)
     PGF_E_DIPLO_OUT = 4,   // -of diplo: not a diploid pair of PAIRS (asDiplo)
-    PGF_E_HWE = 5,         // --HWE with populations: the reference calls an undefined function (inHWE)
+    PGF_E_HWE = 5,         // --HWE with populations: a genotype other than N/N in a population at a variable site (inHWE)
     PGF_E_NFD = 6,         // --nearlyFixedDiff with one population: np.concatenate of nothing
     PGF_E_COUNT = 7,       // -of count at a site without any base (alleles[-1] of an empty list)
     PGF_E_ORDER = 8,       // --alleleOrder freq: an allele that is not among the site's alleles (list.index)
-    PGF_E_POS = 9,         // --thinDist: a position int() does not take, or one beyond 18 digits
+    PGF_E_POS = 9,         // --thinDist: a position int() does not take, or one beyond 18 significant digits
     PGF_E_CELL = 10,       // a genotype of more than PGF_MAXA alleles, or non-ASCII text
     PGF_E_POPSAMPLE = 11,  // a population names a sample that is not selected, and the line reaches that population's filters (KeyError)
 };
@@ -61,6 +61,7 @@ struct PgfCounts {
     int32_t c[4];            // A C G T
     int32_t calls;           // genotypes without a missing allele
     int32_t hets;
+    int32_t not_nn;          // genotypes other than the diploid N/N (whose diplotype "N" inHWE drops)
 };
 
 PGF_HD int pgf_base(char ch) { return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : ch == 'N' ? 4 : -1; }
@@ -146,6 +147,7 @@ PGF_HD void pgf_add(const PgfGeno &g, PgfCounts *c) {
         }
     c->calls += g.missing ? 0 : 1;
     c->hets += g.het ? 1 : 0;
+    c->not_nn += (g.n == 2 && g.a[0] == 'N' && g.a[1] == 'N') ? 0 : 1;
 }
 
 // numpy's argsort of the present bases' counts (int64, 2 to 4 of them), which GenomeSite.alleles(byFreq=True) reverses: numpy's small-
@@ -213,7 +215,13 @@ PGF_HD int pgf_site_test(const PgfConfig &cfg, const PgfCounts &tot, const PgfCo
             if (cfg.min_freq != 0.0 && !(cfg.min_freq <= lo)) return 0;
             if (cfg.max_freq != 0.0 && !(lo <= cfg.max_freq)) return 0;
         }
-        if (cfg.hwe && cfg.n_pops > 0) return -PGF_E_HWE;
+        // --HWE with populations: every population is tested (an empty one is all samples).  inHWE drops the "N" diplotypes and
+        // passes when none is left; any other genotype stops the reference (asDiplo raises, or the undefined `unique` is reached)
+        if (cfg.hwe && cfg.n_pops > 0)
+            for (int k = 0; k < cfg.n_pops; ++k) {
+                if ((cfg.pop_missing >> k) & 1) return -PGF_E_POPSAMPLE;
+                if ((((cfg.pop_empty >> k) & 1) ? tot : pop[k]).not_nn) return -PGF_E_HWE;
+            }
     }
     if (cfg.n_pops >= 1) {
         if (cfg.has_pop_calls)
@@ -385,13 +393,15 @@ PGF_HD bool pgf_thin_keep(bool same_scaf, int64_t pos, int64_t *last_pos, int64_
     return !(pos - *last_pos < thin);
 }
 
-// int(token) for the regular spelling of a position: optional sign, digits (leading zeros kept by the row, not by the value);
-// returns 0 and *v, or PGF_E_POS
+// int(token) for the regular spelling of a position: optional sign, digits (leading zeros kept by the row, not by the value: they
+// do not count towards the 18 digits); returns 0 and *v, or PGF_E_POS
 PGF_HD int pgf_parse_pos(const uint8_t *s, int len, int64_t *v) {
     int k = 0;
     bool neg = false;
     if (k < len && (s[k] == '+' || s[k] == '-')) { neg = s[k] == '-'; ++k; }
-    if (k >= len || len - k > 18) return PGF_E_POS;
+    if (k >= len) return PGF_E_POS;
+    while (k < len - 1 && s[k] == '0') ++k;
+    if (len - k > 18) return PGF_E_POS;
     int64_t x = 0;
     for (; k < len; ++k) {
         if (s[k] < '0' || s[k] > '9') return PGF_E_POS;

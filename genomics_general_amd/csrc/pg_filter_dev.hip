@@ -85,7 +85,7 @@ __device__ inline void field_at(const uint32_t *tabs, int c, int n_cols, uint32_
 __device__ bool line_sums(const FiltArgs &A, const PgfConfig &cfg, const uint8_t *line, const uint32_t *tabs, uint32_t n, int lane,
                           PgfCounts *tot, PgfCounts *pop) {
     int32_t *pw = reinterpret_cast<int32_t *>(pop);
-    for (int k = lane; k < cfg.n_pops * 6; k += 64) pw[k] = 0;
+    for (int k = lane; k < cfg.n_pops * (int)(sizeof(PgfCounts) / 4); k += 64) pw[k] = 0;
     __syncthreads();
     PgfCounts t = {};
     bool bad = false;
@@ -107,6 +107,7 @@ __device__ bool line_sums(const FiltArgs &A, const PgfConfig &cfg, const uint8_t
                 for (int b = 0; b < 4; ++b)
                     if (one.c[b]) atomicAdd(&q.c[b], one.c[b]);
                 if (one.calls) atomicAdd(&q.calls, one.calls);
+                if (one.not_nn) atomicAdd(&q.not_nn, one.not_nn);
             }
         }
     }
@@ -115,6 +116,7 @@ __device__ bool line_sums(const FiltArgs &A, const PgfConfig &cfg, const uint8_t
     for (int b = 0; b < 4; ++b) tot->c[b] = wave_sum(t.c[b]);
     tot->calls = wave_sum(t.calls);
     tot->hets = wave_sum(t.hets);
+    tot->not_nn = wave_sum(t.not_nn);
     return true;
 }
 

@@ -31,13 +31,13 @@ ERRORS = {
        "and never ends)",
     3: "-if diplo: a genotype that is not one of A C G K M N S R T W Y (the reference's worker raises here and never ends)",
     4: "-of diplo: a genotype that is not a diploid pair of A/C/G/T/N the reference knows (the reference's worker raises here and never ends)",
-    5: "--HWE with populations: the reference's HWE test calls an undefined function at the first variable site, its worker dies and "
-       "it never ends; no test is invented here",
+    5: "--HWE with populations: a population holds a genotype other than N/N at a variable site, where the reference's HWE test "
+       "calls an undefined function; its worker dies and it never ends (no test is invented here)",
     6: "--nearlyFixedDiff needs two populations or more (the reference's worker raises here and never ends)",
     7: "-of count at a site without any called base (the reference's worker raises here and never ends)",
     8: "--alleleOrder freq: a genotype holds an allele that is not among the site's alleles (the reference's worker raises here and "
        "never ends)",
-    9: "--thinDist: the position is not an integer of up to 18 digits",
+    9: "--thinDist: the position is not an integer of up to 18 significant digits",
     10: "a genotype of more than 16 alleles, or text that is not ASCII, is not supported",
     11: "a population names a sample that is not among the selected samples, and the line reaches the population filters (the "
         "reference's worker raises KeyError here and never ends)",
