@@ -183,7 +183,7 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
     c->slot_src.release();
     for (int k = 0; k < 2; ++k) {
         pg_ctx::TokSlot &T = c->tok[k];
-        T.text.release(); T.i32.release(); T.dcols.release(); T.pos.release(); T.pos64.release(); T.cells_at.release(); T.i64.release(); T.nl.release(); T.off.release();
+        T.text.release(); T.i32.release(); T.dcols.release(); T.pos.release(); T.pos64.release(); T.cells_at.release(); T.rows8.release(); T.i64.release(); T.nl.release(); T.off.release();
         T.h_total.release(); T.h_pos.release(); T.h_cols.release();
         T.h_head.release(); T.names.release(); T.names_idx.release();
         auto drop = [](pg_ctx::Inflate &I) {
@@ -373,6 +373,7 @@ extern "C" int pg_set_samples(pg_ctx *c, int n_hap, const int32_t *hap_pop, cons
     c->n_pops = n_pops;
     c->n_samp = (int)sstart.size() - 1;
     c->S = (n_hap + 15) / 16 * 16;
+    c->RS = pg_nib_pitch(c->S);
     // plane stride: 32 haplotypes (one tile of the matrix-core pair kernels); the popcount kernels work on 64-lane column chunks
     c->NP = getenv("PG_PAIR_VALU") ? (n_hap + 63) / 64 * 64 : (n_hap + 31) / 32 * 32;
     c->h_pop_start = pstart;
@@ -411,7 +412,7 @@ extern "C" int pg_set_samples(pg_ctx *c, int n_hap, const int32_t *hap_pop, cons
     if (!tasksC.empty() && (rc = c->tasksC.upload(tasksC.data(), tasksC.size(), c->stream)) != PG_OK) return rc;
     if (!tasksCh.empty() && (rc = c->tasksCh.upload(tasksCh.data(), tasksCh.size(), c->stream)) != PG_OK) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
-    // the resident buffer layout depends on S: drop it
+    // the resident buffer layout depends on RS: drop it
     c->gt.release();
     c->cap_sites = 0;
     return PG_OK;
@@ -427,13 +428,43 @@ extern "C" int pg_reserve_sites(pg_ctx *c, int64_t n_sites) {
     HIPCHK(hipStreamSynchronize(c->stream_up));
     c->up_pending = false;
     c->gt.release();
-    int rc = c->gt.alloc((size_t)(n_sites + 32) * c->S);     // +32 rows so a word tile never reads past the end
+    int rc = c->gt.alloc((size_t)(n_sites + 32) * c->RS);    // +32 rows so a word tile never reads past the end
     if (rc != PG_OK) return rc;
-    HIPCHK(hipMemsetAsync(c->gt.p, 0, (size_t)(n_sites + 32) * c->S, c->stream));
+    HIPCHK(hipMemsetAsync(c->gt.p, 0, (size_t)(n_sites + 32) * c->RS, c->stream));
     // the rows are filled through other streams too (asynchronous uploads, the device tokenizer on the copy stream): nothing may
     // be queued there while the clearing is still on its way -- it would wipe rows that were already written
     HIPCHK(hipStreamSynchronize(c->stream));
     c->cap_sites = n_sites;
+    return PG_OK;
+}
+
+// The C-ABI's rows are int8 (one byte per slot); the resident rows hold two slots per byte (pg_nib.h).  Rows on their way in or
+// out pass through the staging buffer at pitch S, at most 256 MiB of them at a time, reused in stream order.
+static int64_t row_stage_rows(const pg_ctx *c) { return std::max<int64_t>(1, ((int64_t)256 << 20) / c->S); }
+
+static int ensure_row_stage(pg_ctx *c, int64_t n) {
+    const size_t need = (size_t)std::min(n, row_stage_rows(c)) * c->S;
+    if (need <= c->cells_stage.cap) return PG_OK;
+    HIPCHK(hipStreamSynchronize(c->stream_up));            // (earlier users of the buffer)
+    return c->cells_stage.alloc(need);
+}
+
+// host int8 rows (any pitch >= n_hap) -> resident rows [off, off + n), queued on st
+static int rows_to_resident(pg_ctx *c, hipStream_t st, int64_t off, const int8_t *gt, int64_t n, int64_t pitch) {
+    int rc = ensure_row_stage(c, n);
+    if (rc != PG_OK) return rc;
+    const int64_t chunk = row_stage_rows(c);
+    for (int64_t a = 0; a < n; a += chunk) {
+        const int64_t m = std::min(chunk, n - a);
+        const int8_t *src = gt + a * pitch;
+        if (pitch == c->S)
+            HIPCHK(hipMemcpyAsync(c->cells_stage.p, src, (size_t)m * c->S, hipMemcpyHostToDevice, st));
+        else
+            HIPCHK(hipMemcpy2DAsync(c->cells_stage.p, c->S, src, (size_t)pitch, c->n_hap, (size_t)m, hipMemcpyHostToDevice, st));
+        pg_launch_nib_pack(st, reinterpret_cast<const int8_t *>(c->cells_stage.p), c->S, c->n_hap, m, c->gt.p + (off + a) * c->RS,
+                           c->RS);
+        HIPCHK(hipGetLastError());
+    }
     return PG_OK;
 }
 
@@ -442,7 +473,10 @@ extern "C" int pg_upload_sites(pg_ctx *c, int64_t off, const int8_t *gt, int64_t
     if (off < 0 || n < 0 || off + n > c->cap_sites) return pg_fail(PG_ERR_ARG, "sites [%lld,%lld) exceed reserved %lld", (long long)off, (long long)(off + n), (long long)c->cap_sites);
     if (n == 0) return PG_OK;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy2DAsync(c->gt.p + off * c->S, c->S, gt, c->n_hap, c->n_hap, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    // (the staging buffer belongs to the copy stream: its queued users are done first)
+    HIPCHK(hipStreamSynchronize(c->stream_up));
+    int rc = rows_to_resident(c, c->stream, off, gt, n, c->n_hap);
+    if (rc != PG_OK) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return PG_OK;
 }
@@ -452,7 +486,17 @@ extern "C" int pg_download_sites(pg_ctx *c, int64_t off, int8_t *gt_out, int64_t
     if (off < 0 || n < 0 || off + n > c->cap_sites) return pg_fail(PG_ERR_ARG, "sites out of range");
     if (n == 0) return PG_OK;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy2DAsync(gt_out, c->n_hap, c->gt.p + off * c->S, c->S, c->n_hap, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream_up));
+    int rc = ensure_row_stage(c, n);
+    if (rc != PG_OK) return rc;
+    const int64_t chunk = row_stage_rows(c);
+    for (int64_t a = 0; a < n; a += chunk) {          // expanded into int8 rows on the device, then one strided D2H per chunk
+        const int64_t m = std::min(chunk, n - a);
+        pg_launch_nib_expand(c->stream, c->gt.p + (off + a) * c->RS, c->RS, m, reinterpret_cast<int8_t *>(c->cells_stage.p), c->S);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy2DAsync(gt_out + a * c->n_hap, c->n_hap, c->cells_stage.p, c->S, c->n_hap, (size_t)m, hipMemcpyDeviceToHost,
+                                c->stream));
+    }
     HIPCHK(hipStreamSynchronize(c->stream));
     return PG_OK;
 }
@@ -463,20 +507,20 @@ extern "C" int pg_move_rows(pg_ctx *c, int64_t src_row, int64_t dst_row, int64_t
         return pg_fail(PG_ERR_ARG, "pg_move_rows: rows out of the reserved range");
     if (n == 0 || src_row == dst_row) return PG_OK;
     HIPCHK(hipSetDevice(c->device));
-    const size_t bytes = (size_t)n * c->S;
+    const size_t bytes = (size_t)n * c->RS;
     const bool overlap = src_row < dst_row + n && dst_row < src_row + n;
     // (on the copy stream: the ingestion thread moves the rows it carries into the half of the resident buffer the next block is
     // tokenised into while the compute stream works on the windows of the current block in the other half)
     hipStream_t st = c->stream_up;
     if (!overlap) {
-        HIPCHK(hipMemcpyAsync(c->gt.p + dst_row * c->S, c->gt.p + src_row * c->S, bytes, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(c->gt.p + dst_row * c->RS, c->gt.p + src_row * c->RS, bytes, hipMemcpyDeviceToDevice, st));
     } else {                                                       // through the (idle) staging buffer of the packed uploads
         if (bytes > c->cells_stage.cap) {
             int rc = c->cells_stage.alloc(bytes);
             if (rc != PG_OK) return rc;
         }
-        HIPCHK(hipMemcpyAsync(c->cells_stage.p, c->gt.p + src_row * c->S, bytes, hipMemcpyDeviceToDevice, st));
-        HIPCHK(hipMemcpyAsync(c->gt.p + dst_row * c->S, c->cells_stage.p, bytes, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(c->cells_stage.p, c->gt.p + src_row * c->RS, bytes, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(c->gt.p + dst_row * c->RS, c->cells_stage.p, bytes, hipMemcpyDeviceToDevice, st));
     }
     HIPCHK(hipStreamSynchronize(st));
     return PG_OK;
@@ -490,17 +534,16 @@ extern "C" int pg_row_pitch(pg_ctx *c, int *pitch_out) {
 }
 
 // Asynchronous upload on the context's copy stream.  The host rows must stay valid (and should be page-locked: pg_host_alloc)
-// until pg_upload_wait returns.  Rows whose pitch equals pg_row_pitch (pad bytes zero) go down as one linear copy.
+// until pg_upload_wait returns.  Rows whose pitch equals pg_row_pitch go down as one linear copy (into the staging buffer, from
+// which k_nib_pack writes the resident rows on the same stream).
 extern "C" int pg_upload_sites_async(pg_ctx *c, int64_t off, const int8_t *gt, int64_t n, int64_t row_pitch) {
     if (!c || (!gt && n > 0)) return pg_fail(PG_ERR_ARG, "pg_upload_sites_async: null argument");
     if (off < 0 || n < 0 || off + n > c->cap_sites) return pg_fail(PG_ERR_ARG, "sites [%lld,%lld) exceed reserved %lld", (long long)off, (long long)(off + n), (long long)c->cap_sites);
     if (row_pitch < c->n_hap) return pg_fail(PG_ERR_ARG, "row pitch %lld is smaller than the %d haplotypes of a row", (long long)row_pitch, c->n_hap);
     if (n == 0) return PG_OK;
     HIPCHK(hipSetDevice(c->device));
-    if (row_pitch == c->S)
-        HIPCHK(hipMemcpyAsync(c->gt.p + off * c->S, gt, (size_t)n * c->S, hipMemcpyHostToDevice, c->stream_up));
-    else
-        HIPCHK(hipMemcpy2DAsync(c->gt.p + off * c->S, c->S, gt, (size_t)row_pitch, c->n_hap, (size_t)n, hipMemcpyHostToDevice, c->stream_up));
+    int rc = rows_to_resident(c, c->stream_up, off, gt, n, row_pitch);
+    if (rc != PG_OK) return rc;
     HIPCHK(hipEventRecord(c->up_ev, c->stream_up));
     c->up_pending = true;
     return PG_OK;
@@ -526,7 +569,7 @@ extern "C" int pg_upload_packed_async(pg_ctx *c, int64_t off, const uint8_t *cel
     int rc = c->slot_src.upload(slot_src, (size_t)c->n_hap, c->stream_up);
     if (rc != PG_OK) return rc;
     HIPCHK(hipMemcpyAsync(c->cells_stage.p, cells, (size_t)n * n_cols, hipMemcpyHostToDevice, c->stream_up));
-    pg_launch_unpack(c->stream_up, c->cells_stage.p, n_cols, n, c->slot_src.p, c->n_hap, c->gt.p + off * c->S, c->S);
+    pg_launch_unpack(c->stream_up, c->cells_stage.p, n_cols, n, c->slot_src.p, c->n_hap, c->gt.p + off * c->RS, c->RS);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->up_ev, c->stream_up));
     c->up_pending = true;
@@ -687,7 +730,7 @@ extern "C" int pg_synth_fill(pg_ctx *c, int64_t off, int64_t n, int64_t first_si
     p.n_dip = n_dip; p.n_pops = n_pops_gen; p.var_thr = var_thr; p.miss_thr = miss_thr;
     hipEvent_t e0, e1;
     if ((rc = pg_time_begin(c, PG_K_SYNTH, &e0, &e1)) != PG_OK) return rc;
-    pg_launch_synth(c->stream, c->gt.p, c->S, c->n_hap, off, n, c->slot_gen.p, p);
+    pg_launch_synth(c->stream, c->gt.p, c->RS, c->n_hap, off, n, c->slot_gen.p, p);
     if ((rc = pg_time_end(c, PG_K_SYNTH, e0, e1, 1)) != PG_OK) return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -856,7 +899,7 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
             HIPCHK(hipEventRecord(e0, ps));
         }
         if (pg_pack_needs_presence(NP) && (rc = sl.pres.ensure((size_t)std::max<int64_t>(ga, 1) * grp * 4)) != PG_OK) return rc;
-        pg_launch_pack2(ps, c->gt.p, c->S, d_lo, d_hi, d_goff, d_vgoff, nb, max_groups, ga, sl.Vp.p, NPv, sl.XV.p, NP,
+        pg_launch_pack2(ps, c->gt.p, c->RS, d_lo, d_hi, d_goff, d_vgoff, nb, max_groups, ga, sl.Vp.p, NPv, sl.XV.p, NP,
                         d_nw, dip ? 1 : 0, c->flag.p, sl.pres.p, capg, grp);
         if (time_pack) {
             HIPCHK(hipEventRecord(e1, ps));
@@ -982,10 +1025,11 @@ extern "C" int pg_reserve_sites_tuned(pg_ctx *c, int64_t n_sites, int max_trials
     if (n_sites < 0) return pg_fail(PG_ERR_ARG, "n_sites < 0");
     HIPCHK(hipSetDevice(c->device));
     if (n_sites <= c->cap_sites) return PG_OK;
-    const size_t bytes = (size_t)(n_sites + 32) * c->S;
+    const size_t bytes = (size_t)(n_sites + 32) * c->RS;
     if (max_trials > 8) max_trials = 8;
     int trials = 1;
-    if (c->n_hap <= 4096 && bytes >= ((size_t)4 << 30) && max_trials > 1) {
+    // (the threshold counts int8-equivalent bytes, one per slot: the same number of sites as before rows held two slots a byte)
+    if (c->n_hap <= 4096 && 2 * bytes >= ((size_t)4 << 30) && max_trials > 1) {
         HIPCHK(hipStreamSynchronize(c->stream_up));
         c->up_pending = false;
         c->gt.release();                                   // (as in pg_reserve_sites: growing drops the rows)
@@ -1642,7 +1686,7 @@ static int quartet_stats(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_
         }
         hipEvent_t e0, e1;
         if ((rc = pg_time_begin(c, PG_K_SITESTATS, &e0, &e1)) != PG_OK) return rc;
-        pg_launch_abba(c->stream, c->gt.p, c->S, c->win.p, c->win.p + nb, nb, max_chunks, c->pop_start.p, p1, p2, p3, p4,
+        pg_launch_abba(c->stream, c->gt.p, c->RS, c->win.p, c->win.p + nb, nb, max_chunks, c->pop_start.p, p1, p2, p3, p4,
                        min_data, sel, nsum, c->part_f64.p, c->part_i64.p, c->res_f64.p, c->res_i64.p, flags, base, np_upto);
         if ((rc = pg_time_end(c, PG_K_SITESTATS, e0, e1, 1)) != PG_OK) return rc;
         HIPCHK(hipGetLastError());
@@ -1707,13 +1751,13 @@ extern "C" int pg_popfreq(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n
         }
         hipEvent_t e0, e1;
         if ((rc = pg_time_begin(c, PG_K_SITESTATS, &e0, &e1)) != PG_OK) return rc;
-        pg_launch_popfreq(c->stream, c->gt.p, c->S, c->n_hap, c->win.p, c->win.p + nb, nb, max_chunks, c->pop_start.p, P, dl, dS, dP,
+        pg_launch_popfreq(c->stream, c->gt.p, c->RS, c->n_hap, c->win.p, c->win.p + nb, nb, max_chunks, c->pop_start.p, P, dl, dS, dP,
                           flags, base);
         if ((rc = pg_time_end(c, PG_K_SITESTATS, e0, e1, 1)) != PG_OK) return rc;
         HIPCHK(hipGetLastError());
         if (flags) {
             if ((rc = pg_time_begin(c, PG_K_ORDERED, &e0, &e1)) != PG_OK) return rc;
-            pg_launch_popfreq_ordered(c->stream, c->gt.p, c->S, c->win.p, c->win.p + nb, nb, c->pop_start.p, P, flags, base, dT);
+            pg_launch_popfreq_ordered(c->stream, c->gt.p, c->RS, c->win.p, c->win.p + nb, nb, c->pop_start.p, P, flags, base, dT);
             if ((rc = pg_time_end(c, PG_K_ORDERED, e0, e1, 1)) != PG_OK) return rc;
             HIPCHK(hipGetLastError());
         }
@@ -1745,7 +1789,7 @@ extern "C" int pg_site_counts(pg_ctx *c, int64_t site_lo, int64_t site_hi, int32
     if (rc != PG_OK) return rc;
     for (int64_t s = site_lo; s < site_hi; s += chunk) {
         int64_t e = std::min(site_hi, s + chunk);
-        pg_launch_site_counts(c->stream, c->gt.p, c->S, s, e, c->pop_start.p, c->n_pops, tmp.p);
+        pg_launch_site_counts(c->stream, c->gt.p, c->RS, s, e, c->pop_start.p, c->n_pops, tmp.p);
         hipError_t err = hipGetLastError();
         if (err == hipSuccess)
             err = hipMemcpyAsync(cnt_out + (size_t)(s - site_lo) * c->n_pops * 4, tmp.p, (size_t)(e - s) * c->n_pops * 16, hipMemcpyDeviceToHost, c->stream);
@@ -1775,7 +1819,7 @@ extern "C" int pg_site_target(pg_ctx *c, int64_t site_lo, int64_t site_hi, int t
     if ((rc = c->site_keep.ensure((size_t)std::min(n, chunk))) != PG_OK) return rc;
     for (int64_t s = site_lo; s < site_hi; s += chunk) {
         const int64_t e = std::min(site_hi, s + chunk);
-        pg_launch_site_counts(c->stream, c->gt.p, c->S, s, e, c->pop_start.p, P, c->site_tmp.p);
+        pg_launch_site_counts(c->stream, c->gt.p, c->RS, s, e, c->pop_start.p, P, c->site_tmp.p);
         pg_launch_site_target(c->stream, c->site_tmp.p, e - s, P, target, min_data, as_counts ? 1 : 0, has_threshold ? 1 : 0, threshold,
                               c->site_val.p, reinterpret_cast<long long *>(c->site_val.p), c->site_keep.p);
         hipError_t err = hipGetLastError();
@@ -1805,7 +1849,7 @@ extern "C" int pg_hap_called(pg_ctx *c, const int64_t *lo, const int64_t *hi, in
         size_t nres = (size_t)nb * c->n_hap;
         if ((rc = c->res_i64.ensure(nres)) != PG_OK) return rc;
         HIPCHK(hipMemsetAsync(c->res_i64.p, 0, nres * 8, c->stream));
-        pg_launch_hap_called(c->stream, c->gt.p, c->S, c->n_hap, c->win.p, c->win.p + nb, nb, max_chunks,
+        pg_launch_hap_called(c->stream, c->gt.p, c->RS, c->n_hap, c->win.p, c->win.p + nb, nb, max_chunks,
                              reinterpret_cast<unsigned long long *>(c->res_i64.p));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(called_out + (size_t)w0 * c->n_hap, c->res_i64.p, nres * 8, hipMemcpyDeviceToHost, c->stream));

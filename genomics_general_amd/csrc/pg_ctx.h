@@ -90,7 +90,8 @@ struct pg_ctx {
     hipStream_t stream = nullptr;
     // samples
     int n_hap = 0, n_pops = 0, n_samp = 0;
-    int S = 0;    // bytes per site row of the resident buffer (multiple of 16, pad = 0)
+    int S = 0;    // haplotype slots per site row (multiple of 16, pad = 0): the int8 row pitch of the C-ABI's host rows
+    int RS = 0;   // bytes per site row of the resident buffer: two slots per byte (pg_nib.h), S / 2
     int NP = 0;   // haplotype stride of the bit-planes (multiple of 32; of 64 for the popcount kernels)
     std::vector<int32_t> h_pop_start, h_samp_start;
     DevBuf<int32_t> hap_pop, pop_start, samp_start, slot_gen;
@@ -111,7 +112,7 @@ struct pg_ctx {
     hipStream_t stream_up = nullptr;
     hipEvent_t up_ev = nullptr;
     bool up_pending = false;
-    DevBuf<uint8_t> cells_stage;     // packed cells of the upload in flight
+    DevBuf<uint8_t> cells_stage;     // packed cells of the upload in flight; int8 rows on their way to / from the resident buffer
     // BGZF members inflated on the device (pg_inflate.hip): compressed bytes, member table, status [error bits, first bad member]
     struct Inflate {
         DevBuf<uint32_t> comp, crc_tab, crc_fold;   // crc_tab: k_crc32's tables; crc_fold: pgi_make_crc_tables (the check inside k_inflate)
@@ -139,6 +140,7 @@ struct pg_ctx {
         DevBuf<int64_t> names_idx;
         DevBuf<int32_t> i32, dcols, pos;
         DevBuf<int64_t> i64, nl, off, pos64, cells_at;
+        DevBuf<int8_t> rows8;              // k_tok_parse (first form): the block's int8 rows, before k_nib_pack
         HostPin<int64_t> h_total;          // page-locked landing: [0] lines, [1] status | runs
         HostPin<int64_t> h_pos;
         HostPin<int32_t> h_cols;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/popgen_hip.h"
+#include "pg_nib.h"
 
 #define PG_MAX_POPS 16          // populations handled by the site-statistics kernels (K3/K6 take any number)
 #define PG_SITES_PER_BLOCK 1024 // sites reduced by one block of the site-statistics kernels
@@ -40,7 +41,12 @@ struct PgSynthParams {
 };
 
 // ---- launchers (all asynchronous on `st`) -----------------------------------------------------------
-void pg_launch_synth(hipStream_t st, int8_t *gt, int S, int n_hap, int64_t site0, int64_t n_sites,
+// Every `gt` is the resident row buffer (two slots per byte, pg_nib.h) and RS its row pitch in bytes.
+
+// int8 rows (pitch S, slots >= n_hap read as 0) -> resident rows; resident rows -> int8 rows (pitch S, every slot of the pitch)
+void pg_launch_nib_pack(hipStream_t st, const int8_t *src, int S, int n_hap, int64_t n_rows, int8_t *gt, int RS);
+void pg_launch_nib_expand(hipStream_t st, const int8_t *gt, int RS, int64_t n_rows, int8_t *dst, int S);
+void pg_launch_synth(hipStream_t st, int8_t *gt, int RS, int n_hap, int64_t site0, int64_t n_sites,
                      const int32_t *slot_gen_hap, PgSynthParams p);
 
 void pg_launch_popdist_fin(hipStream_t st, const int32_t *Cmat, const int32_t *Dmat, int N, int cN, int cshift, int n_win,
@@ -60,28 +66,28 @@ void pg_launch_indpair_fin(hipStream_t st, const int32_t *Cmat, const int32_t *D
                            int64_t *cnt_out, int mean_mode);
 
 
-void pg_launch_abba(hipStream_t st, const int8_t *gt, int S, const int64_t *win_lo, const int64_t *win_hi,
+void pg_launch_abba(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi,
                     int n_win, int max_chunks, const int32_t *pop_start, int p1, int p2, int p3, int p4,
                     double min_data, int sel, int nsum, double *part_sums, int64_t *part_used, double *sums_out,
                     int64_t *used_out, uint32_t *flags, int64_t base, long long max_sites);
 
-void pg_launch_popfreq(hipStream_t st, const int8_t *gt, int S, int n_hap, const int64_t *win_lo,
+void pg_launch_popfreq(hipStream_t st, const int8_t *gt, int RS, int n_hap, const int64_t *win_lo,
                        const int64_t *win_hi, int n_win, int max_chunks, const int32_t *pop_start, int n_pops,
                        unsigned long long *l_out, unsigned long long *S_out, unsigned long long *pairsum_out,
                        uint32_t *flags, int64_t base);
-void pg_launch_popfreq_ordered(hipStream_t st, const int8_t *gt, int S, const int64_t *win_lo, const int64_t *win_hi, int n_win,
+void pg_launch_popfreq_ordered(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi, int n_win,
                                const int32_t *pop_start, int n_pops, const uint32_t *flags, int64_t base, double *theta_out);
 
-void pg_launch_site_counts(hipStream_t st, const int8_t *gt, int S, int64_t site_lo, int64_t site_hi,
+void pg_launch_site_counts(hipStream_t st, const int8_t *gt, int RS, int64_t site_lo, int64_t site_hi,
                            const int32_t *pop_start, int n_pops, int32_t *cnt_out);
 void pg_launch_site_target(hipStream_t st, const int32_t *cnt, int64_t n_sites, int n_pops, int target, double min_data, int as_counts,
                            int has_threshold, double threshold, double *f_out, long long *i_out, uint8_t *keep_out);
 
-void pg_launch_hap_called(hipStream_t st, const int8_t *gt, int S, int n_hap, const int64_t *win_lo,
+void pg_launch_hap_called(hipStream_t st, const int8_t *gt, int RS, int n_hap, const int64_t *win_lo,
                           const int64_t *win_hi, int n_win, int max_chunks, unsigned long long *out);
 
 // ---- pairwise pipeline (pg_pair2.hip) ---------------------------------------------------------------
-void pg_launch_pack2(hipStream_t st, const int8_t *gt, int S, const int64_t *win_lo, const int64_t *win_hi,
+void pg_launch_pack2(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi,
                      const int64_t *goff, const int64_t *vgoff, int n_win, int max_groups, int64_t total_groups, uint32_t *Vp,
                      int NPv, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch, uint32_t *pres, int capg, int grp);
 bool pg_pack_needs_presence(int NP);
@@ -113,7 +119,7 @@ void pg_launch_hapstats(hipStream_t st, const int32_t *Cmat, const int32_t *Dmat
                         const int32_t *pop_start, int n_pops, int max_pop, const int32_t *order, int min_pair_sites, int diag_nan,
                         double max_dist, uint32_t *bits, size_t bits_per_window, double *out);
 void pg_launch_unpack(hipStream_t st, const uint8_t *cells, int n_cols, int64_t n_rows, const int32_t *slot_src, int n_hap,
-                      int8_t *gt, int S);
+                      int8_t *gt, int RS);
 void pg_launch_flag_export(hipStream_t st, int32_t *flag, double *dst);
 void pg_launch_popstats(hipStream_t st, const double *sums, const int64_t *cnts, int n_win, const int32_t *pop_start,
                         int n_pops, double min_data, int do_pairs, double *out, const int64_t *win_lo = nullptr,

@@ -29,10 +29,10 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     return z ^ (z >> 31);
 }
 
-__global__ __launch_bounds__(256) void k_synth(int8_t *__restrict__ gt, int S, int n_hap, int64_t site0,
+__global__ __launch_bounds__(256) void k_synth(int8_t *__restrict__ gt, int RS, int n_hap, int64_t site0,
                                                int64_t n_sites, const int32_t *__restrict__ slot_gen_hap,
                                                PgSynthParams p) {
-    const int groups = S >> 2;
+    const int groups = RS >> 1;                  // thread = 4 slots = 2 bytes of a resident row
     int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     int64_t site = idx / groups;
     int g = (int)(idx - site * groups);
@@ -73,14 +73,14 @@ __global__ __launch_bounds__(256) void k_synth(int8_t *__restrict__ gt, int S, i
         uint32_t code = missing ? 0u : (1u << allele);
         word |= code << (8 * k);
     }
-    *reinterpret_cast<uint32_t *>(gt + (site0 + site) * (int64_t)S + 4 * g) = word;
+    *reinterpret_cast<uint16_t *>(gt + (site0 + site) * (int64_t)RS + 2 * g) = (uint16_t)pg_nib_pack4(word);
 }
 
-void pg_launch_synth(hipStream_t st, int8_t *gt, int S, int n_hap, int64_t site0, int64_t n_sites,
+void pg_launch_synth(hipStream_t st, int8_t *gt, int RS, int n_hap, int64_t site0, int64_t n_sites,
                      const int32_t *slot_gen_hap, PgSynthParams p) {
     // a launch holds at most 2^30 threads: a grid of 2^32 threads or more is silently truncated by the runtime (1e8 sites x 400
     // haplotypes = 1e10 threads filled 14 % of the rows in one launch)
-    const int64_t groups = S >> 2;
+    const int64_t groups = RS >> 1;
     if (n_sites <= 0 || groups <= 0) return;
     const int64_t sites_per_launch = std::max<int64_t>(1, (1ll << 30) / groups);
     for (int64_t a = 0; a < n_sites; a += sites_per_launch) {
@@ -88,7 +88,7 @@ void pg_launch_synth(hipStream_t st, int8_t *gt, int S, int n_hap, int64_t site0
         const int64_t blocks = (n * groups + 255) / 256;
         PgSynthParams q = p;
         q.first_site_index = p.first_site_index + a;
-        hipLaunchKernelGGL(k_synth, dim3((unsigned)blocks), dim3(256), 0, st, gt, S, n_hap, site0 + a, n, slot_gen_hap, q);
+        hipLaunchKernelGGL(k_synth, dim3((unsigned)blocks), dim3(256), 0, st, gt, RS, n_hap, site0 + a, n, slot_gen_hap, q);
     }
 }
 
@@ -544,11 +544,11 @@ void pg_launch_hapstats(hipStream_t st, const int32_t *Cmat, const int32_t *Dmat
 // K_unpack: packed genotype cells -> resident rows, on the device (the host ships 1 byte per diploid
 // genotype -- first allele's one-hot code in the low nibble, second allele's in the high nibble, the `.pgeno` cell -- instead of
 // 1 byte per allele; replaces the host half of what splitSeq / seqArrayToNumArray do in the reference, genomics.py:390-396,
-// 74-77).  Thread = 4 slots of one row; slot_src[slot] = 2 * cell column + allele (or -1: slot stays 0 = missing).
+// 74-77).  Thread = 4 slots (2 bytes) of one row; slot_src[slot] = 2 * cell column + allele (or -1: slot stays 0 = missing).
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_unpack(const uint8_t *__restrict__ cells, int n_cols, int64_t n_rows,
-                                                const int32_t *__restrict__ slot_src, int n_hap, int8_t *__restrict__ gt, int S) {
-    const int groups = S >> 2;
+                                                const int32_t *__restrict__ slot_src, int n_hap, int8_t *__restrict__ gt, int RS) {
+    const int groups = RS >> 1;
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t row = idx / groups;
     if (row >= n_rows) return;
@@ -562,20 +562,72 @@ __global__ __launch_bounds__(256) void k_unpack(const uint8_t *__restrict__ cell
         const int src = slot_src[h];
         if (src < 0) continue;
         const uint32_t cell = c[src >> 1];
-        word |= ((src & 1) ? (cell >> 4) : (cell & 15u)) << (8 * k);
+        word |= ((src & 1) ? (cell >> 4) : (cell & 15u)) << (4 * k);
     }
-    *reinterpret_cast<uint32_t *>(gt + row * (int64_t)S + 4 * g) = word;
+    *reinterpret_cast<uint16_t *>(gt + row * (int64_t)RS + 2 * g) = (uint16_t)word;
 }
 
 void pg_launch_unpack(hipStream_t st, const uint8_t *cells, int n_cols, int64_t n_rows, const int32_t *slot_src, int n_hap,
-                      int8_t *gt, int S) {
-    const int64_t groups = S >> 2;
+                      int8_t *gt, int RS) {
+    const int64_t groups = RS >> 1;
     if (n_rows <= 0 || groups <= 0) return;
     const int64_t rows_per_launch = std::max<int64_t>(1, (1ll << 30) / groups);     // a launch holds at most 2^30 threads
     for (int64_t a = 0; a < n_rows; a += rows_per_launch) {
         const int64_t n = std::min(rows_per_launch, n_rows - a);
         hipLaunchKernelGGL(k_unpack, dim3((unsigned)((n * groups + 255) / 256)), dim3(256), 0, st, cells + a * n_cols, n_cols, n,
-                           slot_src, n_hap, gt + a * (int64_t)S, S);
+                           slot_src, n_hap, gt + a * (int64_t)RS, RS);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// k_nib_pack / k_nib_expand: the C-ABI's int8 rows (pitch S, staged on the device) <-> resident rows (pitch RS = S / 2).
+// Thread = 8 slots = one dword of a resident row.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_nib_pack(const int8_t *__restrict__ src, int S, int n_hap, int64_t n_rows,
+                                                  int8_t *__restrict__ gt, int RS) {
+    const int groups = RS >> 2;
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t row = idx / groups;
+    if (row >= n_rows) return;
+    const int g = (int)(idx - row * groups);
+    const uint2 w = *reinterpret_cast<const uint2 *>(src + row * (int64_t)S + 8 * g);
+    // slots >= n_hap are pad (their staged bytes are whatever the buffer held): 0
+    const int keep = n_hap - 8 * g;
+    const uint64_t m = keep >= 8 ? ~0ull : (keep <= 0 ? 0ull : (1ull << (8 * keep)) - 1ull);
+    const uint32_t lo = w.x & (uint32_t)m & 0x0F0F0F0Fu, hi = w.y & (uint32_t)(m >> 32) & 0x0F0F0F0Fu;
+    *reinterpret_cast<uint32_t *>(gt + row * (int64_t)RS + 4 * g) = pg_nib_pack4(lo) | (pg_nib_pack4(hi) << 16);
+}
+
+__global__ __launch_bounds__(256) void k_nib_expand(const int8_t *__restrict__ gt, int RS, int64_t n_rows, int8_t *__restrict__ dst,
+                                                    int S) {
+    const int groups = RS >> 2;
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t row = idx / groups;
+    if (row >= n_rows) return;
+    const int g = (int)(idx - row * groups);
+    const uint32_t x = *reinterpret_cast<const uint32_t *>(gt + row * (int64_t)RS + 4 * g);
+    *reinterpret_cast<uint2 *>(dst + row * (int64_t)S + 8 * g) = make_uint2(pg_nib_expand4(x & 0xFFFFu), pg_nib_expand4(x >> 16));
+}
+
+void pg_launch_nib_pack(hipStream_t st, const int8_t *src, int S, int n_hap, int64_t n_rows, int8_t *gt, int RS) {
+    const int64_t groups = RS >> 2;
+    if (n_rows <= 0 || groups <= 0) return;
+    const int64_t rows_per_launch = std::max<int64_t>(1, (1ll << 30) / groups);     // a launch holds at most 2^30 threads
+    for (int64_t a = 0; a < n_rows; a += rows_per_launch) {
+        const int64_t n = std::min(rows_per_launch, n_rows - a);
+        hipLaunchKernelGGL(k_nib_pack, dim3((unsigned)((n * groups + 255) / 256)), dim3(256), 0, st, src + a * (int64_t)S, S, n_hap, n,
+                           gt + a * (int64_t)RS, RS);
+    }
+}
+
+void pg_launch_nib_expand(hipStream_t st, const int8_t *gt, int RS, int64_t n_rows, int8_t *dst, int S) {
+    const int64_t groups = RS >> 2;
+    if (n_rows <= 0 || groups <= 0) return;
+    const int64_t rows_per_launch = std::max<int64_t>(1, (1ll << 30) / groups);
+    for (int64_t a = 0; a < n_rows; a += rows_per_launch) {
+        const int64_t n = std::min(rows_per_launch, n_rows - a);
+        hipLaunchKernelGGL(k_nib_expand, dim3((unsigned)((n * groups + 255) / 256)), dim3(256), 0, st, gt + a * (int64_t)RS, RS, n,
+                           dst + a * (int64_t)S, S);
     }
 }
 
@@ -892,23 +944,29 @@ void pg_launch_indpair_fin(hipStream_t st, const int32_t *Cmat, const int32_t *D
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Per-site population base counts (SWAR on one-hot bytes): cnt[b] = #haplotypes of [s,e) with allele b.
-// `row` = the site's S/4 dwords (global memory or an LDS tile row); only the first and last dword of a range need a mask.
+// Per-site population base counts (SWAR on one-hot nibbles): cnt[b] = #haplotypes of [s,e) with allele b.
+// `row` = the site's RS/4 dwords of a resident row (8 slots per dword, pg_nib.h); only the first and last dword of a range need
+// a mask.
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void count_dword(uint32_t v, uint32_t cnt[4]) {
-    cnt[0] += __popc(v & 0x01010101u);
-    cnt[1] += __popc(v & 0x02020202u);
-    cnt[2] += __popc(v & 0x04040404u);
-    cnt[3] += __popc(v & 0x08080808u);
+    cnt[0] += __popc(v & 0x11111111u);
+    cnt[1] += __popc(v & 0x22222222u);
+    cnt[2] += __popc(v & 0x44444444u);
+    cnt[3] += __popc(v & 0x88888888u);
+}
+
+// nibble masks of the first / last dword of the slot range [s,e) (e > s)
+__device__ __forceinline__ uint32_t nib_mask_first(int s) { return ~0u << (4 * (s & 7)); }
+__device__ __forceinline__ uint32_t nib_mask_last(int e) {
+    const int hi = ((e - 1) & 7) + 1;
+    return hi == 8 ? 0xFFFFFFFFu : ((1u << (4 * hi)) - 1u);
 }
 
 __device__ __forceinline__ void range_counts(const uint32_t *__restrict__ row, int s, int e, uint32_t cnt[4]) {
     cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0u;
     if (e <= s) return;
-    const int d0 = s >> 2, d1 = (e - 1) >> 2;
-    const uint32_t m_first = ~((1u << (8 * (s & 3))) - 1u);
-    const int hi = ((e - 1) & 3) + 1;
-    const uint32_t m_last = hi == 4 ? 0xFFFFFFFFu : ((1u << (8 * hi)) - 1u);
+    const int d0 = s >> 3, d1 = (e - 1) >> 3;
+    const uint32_t m_first = nib_mask_first(s), m_last = nib_mask_last(e);
     if (d0 == d1) {
         count_dword(row[d0] & m_first & m_last, cnt);
         return;
@@ -1001,20 +1059,18 @@ __device__ __forceinline__ void quartet_terms(const uint32_t e[8], QuartetAcc<NS
 
 // ------------------------------------------------------------------------------------------------------
 // k_abba_q: four lanes per site, one per population (P1,P2,P3,O).  A wave covers 16 consecutive site rows, i.e. a contiguous
-// 16*S byte span that stays in L1 while the lanes walk their own population's byte range with 16-byte loads; no LDS row
+// 16*RS byte span that stays in L1 while the lanes walk their own population's byte range with 16-byte loads; no LDS row
 // staging, so occupancy is not LDS-limited.  The four lanes of a site exchange counts with quad shuffles; usable sites are
 // appended, in site order, to an LDS list and the float64 phase runs on full waves of list entries.
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void range_counts_x4(const int8_t *__restrict__ rowb, int s, int e, uint32_t cnt[4]) {
     cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0u;
     if (e <= s) return;
-    // bytes [s,e): 16-byte loads from the dword holding s (rows are 16-byte padded and the buffer has slack rows, so reading
-    // a little past e is safe); only the first and the last dword of the range need a byte mask
-    const int b0 = s & ~3;
-    const int last = (e - 1) & ~3;                                         // byte offset of the last dword
-    const uint32_t m_first = ~((1u << (8 * (s & 3))) - 1u);
-    const int hi = ((e - 1) & 3) + 1;
-    const uint32_t m_last = hi == 4 ? 0xFFFFFFFFu : ((1u << (8 * hi)) - 1u);
+    // slots [s,e) of a resident row: 16-byte loads (32 slots) from the dword holding s (rows are 8-byte padded and the buffer
+    // has slack rows, so reading a little past e is safe); only the first and the last dword of the range need a nibble mask
+    const int b0 = (s >> 3) * 4;
+    const int last = ((e - 1) >> 3) * 4;                                   // byte offset of the last dword
+    const uint32_t m_first = nib_mask_first(s), m_last = nib_mask_last(e);
     for (int b = b0; b <= last; b += 16) {
         const uint4 v = *reinterpret_cast<const uint4 *>(rowb + b);
         uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -1029,14 +1085,12 @@ __device__ __forceinline__ void range_counts_x4(const int8_t *__restrict__ rowb,
     }
 }
 
-// OR of the bytes [s,e) of a row: the alleles present among those haplotypes (low 4 bits)
+// OR of the slots [s,e) of a resident row: the alleles present among those haplotypes (low 4 bits)
 __device__ __forceinline__ uint32_t range_presence_x4(const int8_t *__restrict__ rowb, int s, int e) {
     if (e <= s) return 0u;
-    const int b0 = s & ~3;
-    const int last = (e - 1) & ~3;
-    const uint32_t m_first = ~((1u << (8 * (s & 3))) - 1u);
-    const int hi = ((e - 1) & 3) + 1;
-    const uint32_t m_last = hi == 4 ? 0xFFFFFFFFu : ((1u << (8 * hi)) - 1u);
+    const int b0 = (s >> 3) * 4;
+    const int last = ((e - 1) >> 3) * 4;
+    const uint32_t m_first = nib_mask_first(s), m_last = nib_mask_last(e);
     uint32_t acc = 0u;
     for (int b = b0; b <= last; b += 16) {
         const uint4 v = *reinterpret_cast<const uint4 *>(rowb + b);
@@ -1052,43 +1106,44 @@ __device__ __forceinline__ uint32_t range_presence_x4(const int8_t *__restrict__
     }
     acc |= acc >> 16;
     acc |= acc >> 8;
+    acc |= acc >> 4;
     return acc & 0xFu;
 }
 
-// Row loads of the screening passes (k_abba_q, k_popfreq_q): 16 lanes per row, NPASS passes of 256 bytes, 4 rows per
-// instruction, GROUPS instructions per pass and step.
-typedef uint32_t pg_u32x4 __attribute__((ext_vector_type(4)));
+// Row loads of the screening passes (k_abba_q, k_popfreq_q): 16 lanes per row, NPASS passes of 256 slots (128 bytes of a
+// resident row; 8 bytes = 16 slots per lane), 4 rows per instruction, GROUPS instructions per pass and step.
+typedef uint32_t pg_u32x2 __attribute__((ext_vector_type(2)));
 
 template <int GROUPS, int NPASS>
 struct ScreenLoads {
     __amdgpu_buffer_rsrc_t rsrc;
     int voff[NPASS];                  // lane offset of pass p; beyond the descriptor for lanes past the end of a row
     int soff[GROUPS];                 // g * 4 rows, kept in SGPRs
-    int S;
+    int RS;
     int64_t c0;
-    __device__ __forceinline__ ScreenLoads(const int8_t *gt, int S_, int64_t c0_, int64_t c1, int sub, int rsel) : S(S_), c0(c0_) {
-        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(gt + c0_ * (int64_t)S_), 0, (int)(c1 - c0_) * S_, 0x00020000);
+    __device__ __forceinline__ ScreenLoads(const int8_t *gt, int RS_, int64_t c0_, int64_t c1, int sub, int rsel) : RS(RS_), c0(c0_) {
+        rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(gt + c0_ * (int64_t)RS_), 0, (int)(c1 - c0_) * RS_, 0x00020000);
 #pragma unroll
         for (int p = 0; p < NPASS; ++p) {
-            const int off = p * 256 + sub * 16;
-            voff[p] = off < S_ ? rsel * S_ + off : 0x7ffffff0;
+            const int off = p * 128 + sub * 8;
+            voff[p] = off < RS_ ? rsel * RS_ + off : 0x7ffffff0;
         }
 #pragma unroll
         for (int g = 0; g < GROUPS; ++g) {
-            int t = g * 4 * S_;
+            int t = g * 4 * RS_;
             asm volatile("" : "+s"(t));
             soff[g] = t;
         }
     }
-    __device__ __forceinline__ void issue(int64_t t0, uint4 (&v)[GROUPS][NPASS]) const {
+    __device__ __forceinline__ void issue(int64_t t0, uint2 (&v)[GROUPS][NPASS]) const {
         const int64_t rel = t0 - c0;
-        const int base = rel < (1 << 20) ? (int)rel * S : 0x7ffffff0;          // far past the block: everything reads as zero
+        const int base = rel < (1 << 20) ? (int)rel * RS : 0x7ffffff0;         // far past the block: everything reads as zero
 #pragma unroll
         for (int g = 0; g < GROUPS; ++g)
 #pragma unroll
             for (int p = 0; p < NPASS; ++p) {
-                const pg_u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff[p] + base, soff[g], 0);
-                v[g][p] = make_uint4(r.x, r.y, r.z, r.w);
+                const pg_u32x2 r = __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff[p] + base, soff[g], 0);
+                v[g][p] = make_uint2(r.x, r.y);
             }
     }
 };
@@ -1106,7 +1161,7 @@ struct ScreenLoads {
 // bytes) and ORs them over the 16 lanes with DPP row shifts; NPASS == 0: rows longer than 1024 bytes, screened with the
 // counting pass's quad layout.
 template <int NSUM, int NPASS>
-__global__ __launch_bounds__(256) void k_abba_q(const int8_t *__restrict__ gt, int S, const int64_t *__restrict__ win_lo,
+__global__ __launch_bounds__(256) void k_abba_q(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
                                                 const int64_t *__restrict__ win_hi, int max_chunks,
                                                 const int32_t *__restrict__ pop_start, int q1, int q2, int q3, int q4,
                                                 double min_data, int sel, double *__restrict__ part_sums,
@@ -1140,7 +1195,7 @@ __global__ __launch_bounds__(256) void k_abba_q(const int8_t *__restrict__ gt, i
     // usable sites appended to the float64 ring.
     auto count_sites = [&](int64_t site, bool valid) {
             uint32_t cnt[4] = {0u, 0u, 0u, 0u};
-            if (valid) range_counts_x4(gt + site * (int64_t)S, my_s, my_e, cnt);
+            if (valid) range_counts_x4(gt + site * (int64_t)RS, my_s, my_e, cnt);
             const uint32_t n = cnt[0] + cnt[1] + cnt[2] + cnt[3];
             int ok = valid && ((int)n >= my_nmin);
             ok &= __shfl_xor(ok, 1, 64);
@@ -1217,22 +1272,22 @@ __global__ __launch_bounds__(256) void k_abba_q(const int8_t *__restrict__ gt, i
         // row bytes, a fraction of the counting work).  Only sites with exactly two alleles can pass genomics.py:1655 / :1593;
         // they are queued in site order and counted 16 at a time (their rows are re-read, from cache where possible).
         // A wave owns 16 consecutive sites per step; the whole loop is wave-synchronous (no block barrier).
-        // bytes of this lane's 16-byte pieces that belong to one of the four populations
-        uint32_t umask[NPASS > 0 ? NPASS : 1][4];
+        // nibbles of this lane's 16-slot pieces that belong to one of the four populations
+        uint32_t umask[NPASS > 0 ? NPASS : 1][2];
         const int sub = lane & 15, rsel = lane >> 4;
         if (NPASS > 0) {
 #pragma unroll
             for (int p = 0; p < NPASS; ++p)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
+                for (int k = 0; k < 2; ++k) {
                     uint32_t m = 0u;
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        const int x = p * 256 + sub * 16 + 4 * k + b;
+                    for (int b = 0; b < 8; ++b) {
+                        const int x = p * 256 + sub * 16 + 8 * k + b;
                         bool in = false;
 #pragma unroll
                         for (int z = 0; z < 4; ++z) in = in || (x >= pop_start[qs[z]] && x < pop_start[qs[z] + 1]);
-                        if (in) m |= 0xFFu << (8 * b);
+                        if (in) m |= 0xFu << (4 * b);
                     }
                     umask[p][k] = m;
                 }
@@ -1240,16 +1295,14 @@ __global__ __launch_bounds__(256) void k_abba_q(const int8_t *__restrict__ gt, i
         if (NPASS > 0) {
             // see ScreenLoads: zero-filling buffer loads, the loads of step k+1 issued before step k is processed
             constexpr int GROUPS = NPASS > 0 ? 8 / NPASS : 1, SPW = 4 * GROUPS, NP1 = NPASS > 0 ? NPASS : 1;
-            const ScreenLoads<GROUPS, NP1> sl(gt, S, c0, c1, sub, rsel);
-            auto process = [&](int64_t t0, const uint4 (&v)[GROUPS][NP1]) {
+            const ScreenLoads<GROUPS, NP1> sl(gt, RS, c0, c1, sub, rsel);
+            auto process = [&](int64_t t0, const uint2 (&v)[GROUPS][NP1]) {
 #pragma unroll
                 for (int g = 0; g < GROUPS; ++g) {
                     const int64_t site = t0 + 4 * g + rsel;
                     uint32_t acc = 0u;
 #pragma unroll
-                    for (int p = 0; p < NP1; ++p)
-                        acc |= (v[g][p].x & umask[p][0]) | (v[g][p].y & umask[p][1]) | (v[g][p].z & umask[p][2]) |
-                               (v[g][p].w & umask[p][3]);
+                    for (int p = 0; p < NP1; ++p) acc |= (v[g][p].x & umask[p][0]) | (v[g][p].y & umask[p][1]);
 #define PG_DPP_ROW_OR(ctrl) acc |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)acc, ctrl, 0xf, 0xf, false)
                     PG_DPP_ROW_OR(0x111);        // row_shr:1
                     PG_DPP_ROW_OR(0x112);        // row_shr:2
@@ -1258,6 +1311,7 @@ __global__ __launch_bounds__(256) void k_abba_q(const int8_t *__restrict__ gt, i
 #undef PG_DPP_ROW_OR
                     acc |= acc >> 16;
                     acc |= acc >> 8;
+                    acc |= acc >> 4;
                     const bool is_cand = sub == 15 && site < c1 && __popc(acc & 0xFu) == 2;
                     const unsigned long long bal = __ballot(is_cand);
                     if (is_cand) my_cand[(ctail + __popcll(bal & ((1ull << lane) - 1ull))) & (PG_ABBA_CAND - 1)] = site;
@@ -1268,7 +1322,7 @@ __global__ __launch_bounds__(256) void k_abba_q(const int8_t *__restrict__ gt, i
                     chead += 16;
                 }
             };
-            uint4 va[GROUPS][NP1], vb[GROUPS][NP1];
+            uint2 va[GROUPS][NP1], vb[GROUPS][NP1];
             int64_t t0 = c0 + SPW * wave;
             sl.issue(t0, va);
             while (t0 < c1) {
@@ -1283,7 +1337,7 @@ __global__ __launch_bounds__(256) void k_abba_q(const int8_t *__restrict__ gt, i
         } else {
             for (int64_t t0 = c0 + 16 * wave; t0 < c1; t0 += 64) {
                 const int64_t site = t0 + (lane >> 2);
-                uint32_t pres = site < c1 ? range_presence_x4(gt + site * (int64_t)S, my_s, my_e) : 0u;
+                uint32_t pres = site < c1 ? range_presence_x4(gt + site * (int64_t)RS, my_s, my_e) : 0u;
                 pres |= (uint32_t)__shfl_xor((int)pres, 1, 64);
                 pres |= (uint32_t)__shfl_xor((int)pres, 2, 64);
                 const bool is_cand = q == 0 && __popc(pres) == 2;
@@ -1355,7 +1409,7 @@ __global__ void k_abba_reduce(const double *__restrict__ part_sums, const int64_
 // per sum --, and the tree above the runs is followed with a small stack (its depth is at most 7 + the chain of pieces).
 // ------------------------------------------------------------------------------------------------------
 template <int NSUM>
-__global__ __launch_bounds__(64) void k_quartet_np(const int8_t *__restrict__ gt, int S, const int64_t *__restrict__ win_lo,
+__global__ __launch_bounds__(64) void k_quartet_np(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
                                                    const int64_t *__restrict__ win_hi, const int32_t *__restrict__ pop_start, int q1,
                                                    int q2, int q3, int q4, int sel, const uint32_t *__restrict__ flags, int64_t base,
                                                    double *__restrict__ sums_out, long long max_sites) {
@@ -1436,7 +1490,7 @@ __global__ __launch_bounds__(64) void k_quartet_np(const int8_t *__restrict__ gt
             int take = len - filled < list_len - list_pos ? len - filled : list_len - list_pos;
             if (take > 64) take = 64;
             if (lane < take) {
-                const int8_t *rowb = gt + (step_site0 + list[list_pos + lane]) * (int64_t)S;
+                const int8_t *rowb = gt + (step_site0 + list[list_pos + lane]) * (int64_t)RS;
                 uint32_t cnt[4][4], nk[4], tot[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -1543,7 +1597,7 @@ __global__ __launch_bounds__(64) void k_quartet_np(const int8_t *__restrict__ gt
     if (lane < NSUM) sums_out[(size_t)win * NSUM + lane] = total;
 }
 
-void pg_launch_abba(hipStream_t st, const int8_t *gt, int S, const int64_t *win_lo, const int64_t *win_hi,
+void pg_launch_abba(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi,
                     int n_win, int max_chunks, const int32_t *pop_start, int p1, int p2, int p3, int p4,
                     double min_data, int sel, int nsum, double *part_sums, int64_t *part_used, double *sums_out,
                     int64_t *used_out, uint32_t *flags, int64_t base, long long max_sites) {
@@ -1551,9 +1605,9 @@ void pg_launch_abba(hipStream_t st, const int8_t *gt, int S, const int64_t *win_
     if (max_chunks > 0) {
         const dim3 grid(max_chunks, n_win);
 #define PG_ABBA_LAUNCH(NS, NP)                                                                                          \
-    hipLaunchKernelGGL((k_abba_q<NS, NP>), grid, dim3(256), 0, st, gt, S, win_lo, win_hi, max_chunks, pop_start, p1, p2, \
+    hipLaunchKernelGGL((k_abba_q<NS, NP>), grid, dim3(256), 0, st, gt, RS, win_lo, win_hi, max_chunks, pop_start, p1, p2, \
                        p3, p4, min_data, sel, part_sums, part_used, flags, base)
-        const int npass = (S + 255) / 256;
+        const int npass = (2 * RS + 255) / 256;                             // passes of 256 slots
         if (nsum == PG_ABBA_NSUM) {
             if (npass == 1) PG_ABBA_LAUNCH(PG_ABBA_NSUM, 1);
             else if (npass == 2) PG_ABBA_LAUNCH(PG_ABBA_NSUM, 2);
@@ -1572,10 +1626,10 @@ void pg_launch_abba(hipStream_t st, const int8_t *gt, int S, const int64_t *win_
                        max_chunks, nsum, win_lo, win_hi, sums_out, used_out);
     if (flags) {                                                         // the sums again, in NumPy's order (the counts stay)
         if (nsum == PG_ABBA_NSUM)
-            hipLaunchKernelGGL((k_quartet_np<PG_ABBA_NSUM>), dim3(n_win), dim3(64), 0, st, gt, S, win_lo, win_hi, pop_start, p1, p2, p3,
+            hipLaunchKernelGGL((k_quartet_np<PG_ABBA_NSUM>), dim3(n_win), dim3(64), 0, st, gt, RS, win_lo, win_hi, pop_start, p1, p2, p3,
                                p4, sel, flags, base, sums_out, max_sites);
         else
-            hipLaunchKernelGGL((k_quartet_np<PG_FOURPOP_NSUM>), dim3(n_win), dim3(64), 0, st, gt, S, win_lo, win_hi, pop_start, p1, p2,
+            hipLaunchKernelGGL((k_quartet_np<PG_FOURPOP_NSUM>), dim3(n_win), dim3(64), 0, st, gt, RS, win_lo, win_hi, pop_start, p1, p2,
                                p3, p4, sel, flags, base, sums_out, max_sites);
     }
 }
@@ -1611,7 +1665,7 @@ __device__ __forceinline__ void popfreq_site(const uint32_t *__restrict__ row, i
 }
 
 // Rows longer than 1024 bytes (more than 1024 haplotype slots): one thread per site straight from global memory.
-__global__ __launch_bounds__(256) void k_popfreq(const int8_t *__restrict__ gt, int S, int n_hap,
+__global__ __launch_bounds__(256) void k_popfreq(const int8_t *__restrict__ gt, int RS, int n_hap,
                                                  const int64_t *__restrict__ win_lo, const int64_t *__restrict__ win_hi,
                                                  const int32_t *__restrict__ pop_start, int n_pops,
                                                  unsigned long long *__restrict__ l_out,
@@ -1629,7 +1683,7 @@ __global__ __launch_bounds__(256) void k_popfreq(const int8_t *__restrict__ gt, 
     for (int q = 0; q < PG_MAX_POPS; ++q) { F.Sx[q] = 0; F.Px[q] = 0; }
     const int64_t c1 = (c0 + PG_SITES_PER_BLOCK < hi) ? c0 + PG_SITES_PER_BLOCK : hi;
     for (int64_t t = c0 + threadIdx.x; t < c1; t += blockDim.x)
-        popfreq_site(reinterpret_cast<const uint32_t *>(gt + t * (int64_t)S), n_hap, pop_start, n_pops, F, flags, t - base);
+        popfreq_site(reinterpret_cast<const uint32_t *>(gt + t * (int64_t)RS), n_hap, pop_start, n_pops, F, flags, t - base);
     __syncthreads();
     unsigned long long r = block_sum_u64(F.l, shu);
     if (threadIdx.x == 0 && r) atomicAdd(&l_out[win], r);
@@ -1642,11 +1696,11 @@ __global__ __launch_bounds__(256) void k_popfreq(const int8_t *__restrict__ gt, 
 }
 
 // k_popfreq_q: same structure as k_abba_q.  Screening pass: a site takes part iff every haplotype slot is called
-// (genomics.py:1010); called codes are one-hot and pad bytes zero, so that is popcount(row) == n_hap -- four accumulating
-// v_bcnt per 16-byte piece on fully coalesced loads, summed over the 16 lanes of a row with DPP.  Counting pass, 16 queued
+// (genomics.py:1010); called codes are one-hot and pad nibbles zero, so that is popcount(row) == n_hap -- two accumulating
+// v_bcnt per 8-byte piece (16 slots) on fully coalesced loads, summed over the 16 lanes of a row with DPP.  Counting pass, 16 queued
 // sites at a time: lane q of a site's quad counts populations q, q+4, q+8, q+12.
 template <int NPASS>
-__global__ __launch_bounds__(256) void k_popfreq_q(const int8_t *__restrict__ gt, int S, int n_hap,
+__global__ __launch_bounds__(256) void k_popfreq_q(const int8_t *__restrict__ gt, int RS, int n_hap,
                                                    const int64_t *__restrict__ win_lo, const int64_t *__restrict__ win_hi,
                                                    const int32_t *__restrict__ pop_start, int n_pops,
                                                    unsigned long long *__restrict__ l_out,
@@ -1672,7 +1726,7 @@ __global__ __launch_bounds__(256) void k_popfreq_q(const int8_t *__restrict__ gt
     for (int z = 0; z < 9; ++z) my_acc[z][lane] = 0ull;          // l, Sx[0..3], Px[0..3] for populations q, q+4, q+8, q+12
     auto count_sites = [&](int64_t site, bool valid) {
         if (!valid) return;
-        const int8_t *rowb = gt + site * (int64_t)S;
+        const int8_t *rowb = gt + site * (int64_t)RS;
         if (q == 0) my_acc[0][lane] += 1ull;
 #pragma unroll 1
         for (int j = 0; j < 4; ++j) {
@@ -1691,17 +1745,16 @@ __global__ __launch_bounds__(256) void k_popfreq_q(const int8_t *__restrict__ gt
     };
     // Screening loads: raw buffer loads on a descriptor of the block's rows (rows past the window and the lanes past the end
     // of a row read as zero: no predication, no address arithmetic beyond one add per step), and the loads of step k+1 are
-    // issued before step k is processed, so a wave always has GROUPS*NPASS .. 2*GROUPS*NPASS 16-byte loads in flight.
+    // issued before step k is processed, so a wave always has GROUPS*NPASS .. 2*GROUPS*NPASS 8-byte loads in flight.
     constexpr int GROUPS = 8 / NPASS, SPW = 4 * GROUPS;
-    const ScreenLoads<GROUPS, NPASS> sl(gt, S, c0, c1, sub, rsel);
-    auto process = [&](int64_t t0, const uint4 (&v)[GROUPS][NPASS]) {
+    const ScreenLoads<GROUPS, NPASS> sl(gt, RS, c0, c1, sub, rsel);
+    auto process = [&](int64_t t0, const uint2 (&v)[GROUPS][NPASS]) {
 #pragma unroll
         for (int g = 0; g < GROUPS; ++g) {
             const int64_t site = t0 + 4 * g + rsel;
             uint32_t cnt = 0u;
 #pragma unroll
-            for (int p = 0; p < NPASS; ++p)
-                cnt += __popc(v[g][p].x) + __popc(v[g][p].y) + __popc(v[g][p].z) + __popc(v[g][p].w);
+            for (int p = 0; p < NPASS; ++p) cnt += __popc(v[g][p].x) + __popc(v[g][p].y);
 #define PG_DPP_ROW_ADD(ctrl) cnt += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)cnt, ctrl, 0xf, 0xf, false)
             PG_DPP_ROW_ADD(0x111);        // row_shr:1
             PG_DPP_ROW_ADD(0x112);        // row_shr:2
@@ -1719,7 +1772,7 @@ __global__ __launch_bounds__(256) void k_popfreq_q(const int8_t *__restrict__ gt
         }
     };
     {
-        uint4 va[GROUPS][NPASS], vb[GROUPS][NPASS];
+        uint2 va[GROUPS][NPASS], vb[GROUPS][NPASS];
         int64_t t0 = c0 + SPW * wave;
         sl.issue(t0, va);
         while (t0 < c1) {
@@ -1773,7 +1826,7 @@ __global__ __launch_bounds__(256) void k_popfreq_q(const int8_t *__restrict__ gt
 // left (1 bit per site: every slot called and some population polymorphic; all other sites add 0.0, which changes nothing),
 // 2048 sites per step: the flagged sites are listed in site order, their per-population values are formed 64 sites at a time
 // (one site per lane), and lane p adds the values of population p one after the other.
-__global__ __launch_bounds__(64) void k_popfreq_ordered(const int8_t *__restrict__ gt, int S, const int64_t *__restrict__ win_lo,
+__global__ __launch_bounds__(64) void k_popfreq_ordered(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
                                                         const int64_t *__restrict__ win_hi, const int32_t *__restrict__ pop_start,
                                                         int n_pops, const uint32_t *__restrict__ flags, int64_t base,
                                                         double *__restrict__ theta_out) {
@@ -1831,7 +1884,7 @@ __global__ __launch_bounds__(64) void k_popfreq_ordered(const int8_t *__restrict
             for (int b0 = 0; b0 < total; b0 += 64) {
                 const int nb = total - b0 < 64 ? total - b0 : 64;
                 if (lane < nb) {
-                    const int8_t *rowb = gt + (base + (q0 << 7) + list[b0 + lane]) * (int64_t)S;
+                    const int8_t *rowb = gt + (base + (q0 << 7) + list[b0 + lane]) * (int64_t)RS;
                     for (int p = 0; p < n_pops; ++p) {
                         const int ps = pop_start[p], pe = pop_start[p + 1];
                         uint32_t c[4];
@@ -1853,44 +1906,44 @@ __global__ __launch_bounds__(64) void k_popfreq_ordered(const int8_t *__restrict
     if (lane < n_pops) theta_out[(size_t)win * n_pops + lane] = acc;
 }
 
-void pg_launch_popfreq(hipStream_t st, const int8_t *gt, int S, int n_hap, const int64_t *win_lo,
+void pg_launch_popfreq(hipStream_t st, const int8_t *gt, int RS, int n_hap, const int64_t *win_lo,
                        const int64_t *win_hi, int n_win, int max_chunks, const int32_t *pop_start, int n_pops,
                        unsigned long long *l_out, unsigned long long *S_out, unsigned long long *pairsum_out,
                        uint32_t *flags, int64_t base) {
     if (n_win <= 0 || max_chunks <= 0) return;
-    const int npass = (S + 255) / 256;
-    if (npass <= 4) {                 // rows up to 1024 bytes: screening + counting kernel, 4096-site blocks
+    const int npass = (2 * RS + 255) / 256;                               // passes of 256 slots
+    if (npass <= 4) {                 // rows up to 1024 slots: screening + counting kernel, 4096-site blocks
         const int chunks_q = (int)(((int64_t)max_chunks * PG_SITES_PER_BLOCK + PG_ABBA_SITES_PER_BLOCK - 1) / PG_ABBA_SITES_PER_BLOCK);
         const dim3 grid(chunks_q, n_win);
 #define PG_POPFREQ_LAUNCH(NP)                                                                                           \
-    hipLaunchKernelGGL((k_popfreq_q<NP>), grid, dim3(256), 0, st, gt, S, n_hap, win_lo, win_hi, pop_start, n_pops, l_out, \
+    hipLaunchKernelGGL((k_popfreq_q<NP>), grid, dim3(256), 0, st, gt, RS, n_hap, win_lo, win_hi, pop_start, n_pops, l_out, \
                        S_out, pairsum_out, flags, base)
         if (npass == 1) PG_POPFREQ_LAUNCH(1);
         else if (npass == 2) PG_POPFREQ_LAUNCH(2);
         else PG_POPFREQ_LAUNCH(4);
 #undef PG_POPFREQ_LAUNCH
     } else {
-        hipLaunchKernelGGL(k_popfreq, dim3(max_chunks, n_win), dim3(256), 0, st, gt, S, n_hap, win_lo, win_hi, pop_start, n_pops,
+        hipLaunchKernelGGL(k_popfreq, dim3(max_chunks, n_win), dim3(256), 0, st, gt, RS, n_hap, win_lo, win_hi, pop_start, n_pops,
                            l_out, S_out, pairsum_out, flags, base);
     }
 }
 
-void pg_launch_popfreq_ordered(hipStream_t st, const int8_t *gt, int S, const int64_t *win_lo, const int64_t *win_hi, int n_win,
+void pg_launch_popfreq_ordered(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi, int n_win,
                                const int32_t *pop_start, int n_pops, const uint32_t *flags, int64_t base, double *theta_out) {
     if (n_win <= 0) return;
-    hipLaunchKernelGGL(k_popfreq_ordered, dim3(n_win), dim3(64), 0, st, gt, S, win_lo, win_hi, pop_start, n_pops, flags, base,
+    hipLaunchKernelGGL(k_popfreq_ordered, dim3(n_win), dim3(64), 0, st, gt, RS, win_lo, win_hi, pop_start, n_pops, flags, base,
                        theta_out);
 }
 
 // ------------------------------------------------------------------------------------------------------
 // K_counts: cnt[site][pop][4]
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_site_counts(const int8_t *__restrict__ gt, int S, int64_t site_lo,
+__global__ __launch_bounds__(256) void k_site_counts(const int8_t *__restrict__ gt, int RS, int64_t site_lo,
                                                      int64_t site_hi, const int32_t *__restrict__ pop_start, int n_pops,
                                                      int32_t *__restrict__ cnt_out) {
     const int64_t site = site_lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (site >= site_hi) return;
-    const uint32_t *row = reinterpret_cast<const uint32_t *>(gt + site * (int64_t)S);
+    const uint32_t *row = reinterpret_cast<const uint32_t *>(gt + site * (int64_t)RS);
     for (int q = 0; q < n_pops; ++q) {
         uint32_t c[4];
         range_counts(row, pop_start[q], pop_start[q + 1], c);
@@ -1899,11 +1952,11 @@ __global__ __launch_bounds__(256) void k_site_counts(const int8_t *__restrict__ 
     }
 }
 
-void pg_launch_site_counts(hipStream_t st, const int8_t *gt, int S, int64_t site_lo, int64_t site_hi,
+void pg_launch_site_counts(hipStream_t st, const int8_t *gt, int RS, int64_t site_lo, int64_t site_hi,
                            const int32_t *pop_start, int n_pops, int32_t *cnt_out) {
     int64_t n = site_hi - site_lo;
     if (n <= 0 || n_pops <= 0) return;
-    hipLaunchKernelGGL(k_site_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gt, S, site_lo, site_hi,
+    hipLaunchKernelGGL(k_site_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gt, RS, site_lo, site_hi,
                        pop_start, n_pops, cnt_out);
 }
 
@@ -1986,7 +2039,7 @@ void pg_launch_site_target(hipStream_t st, const int32_t *cnt, int64_t n_sites, 
 // ------------------------------------------------------------------------------------------------------
 // K_called: per-window, per-haplotype number of called sites (Alignment.seqNonNan, genomics.py:1038-1040).
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_hap_called(const int8_t *__restrict__ gt, int S, int n_hap,
+__global__ __launch_bounds__(256) void k_hap_called(const int8_t *__restrict__ gt, int RS, int n_hap,
                                                     const int64_t *__restrict__ win_lo, const int64_t *__restrict__ win_hi,
                                                     unsigned long long *__restrict__ out) {
     const int win = blockIdx.y;
@@ -1999,7 +2052,7 @@ __global__ __launch_bounds__(256) void k_hap_called(const int8_t *__restrict__ g
         uint32_t acc = 0u;
         int pending = 0;
         for (int64_t s = c0; s < c1; ++s) {
-            const uint32_t d = *reinterpret_cast<const uint32_t *>(gt + s * (int64_t)S + 4 * g);
+            const uint32_t d = pg_nib_expand4(*reinterpret_cast<const uint16_t *>(gt + s * (int64_t)RS + 2 * g));
             acc += (d | (d >> 1) | (d >> 2) | (d >> 3)) & 0x01010101u;
             if (++pending == 255) {
 #pragma unroll
@@ -2016,8 +2069,8 @@ __global__ __launch_bounds__(256) void k_hap_called(const int8_t *__restrict__ g
     }
 }
 
-void pg_launch_hap_called(hipStream_t st, const int8_t *gt, int S, int n_hap, const int64_t *win_lo,
+void pg_launch_hap_called(hipStream_t st, const int8_t *gt, int RS, int n_hap, const int64_t *win_lo,
                           const int64_t *win_hi, int n_win, int max_chunks, unsigned long long *out) {
     if (n_win <= 0 || max_chunks <= 0) return;
-    hipLaunchKernelGGL(k_hap_called, dim3(max_chunks, n_win), dim3(256), 0, st, gt, S, n_hap, win_lo, win_hi, out);
+    hipLaunchKernelGGL(k_hap_called, dim3(max_chunks, n_win), dim3(256), 0, st, gt, RS, n_hap, win_lo, win_hi, out);
 }

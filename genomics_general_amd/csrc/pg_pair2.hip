@@ -74,33 +74,46 @@ __device__ __forceinline__ void btrans4(uint32_t t0, uint32_t t1, uint32_t t2, u
 // address arithmetic at all.
 struct RowOff { int v[16]; };
 
-__device__ __forceinline__ RowOff make_row_off(int S) {
+__device__ __forceinline__ RowOff make_row_off(int RS) {
     RowOff ro;
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
-        int t = s * S;
+        int t = s * RS;
         asm volatile("" : "+s"(t));          // opaque: stays in an SGPR instead of being rematerialised per load
         ro.v[s] = t;
     }
     return ro;
 }
 
-__device__ __forceinline__ void word_load(__amdgpu_buffer_rsrc_t rsrc, int h0, int S, int row0, const RowOff &ro, uint32_t d[32]) {
-    const int v0 = h0 + row0 * S, v1 = v0 + 16 * S;
+// b0 = byte offset of the lane's piece of a row, RS = row pitch in bytes: one dword (k_pack3: 8 slots) per row
+__device__ __forceinline__ void word_load(__amdgpu_buffer_rsrc_t rsrc, int b0, int RS, int row0, const RowOff &ro, uint32_t d[32]) {
+    const int v0 = b0 + row0 * RS, v1 = v0 + 16 * RS;
 #pragma unroll
     for (int s = 0; s < 16; ++s) d[s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, v0, ro.v[s], 0);
 #pragma unroll
     for (int s = 0; s < 16; ++s) d[16 + s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, v1, ro.v[s], 0);
 }
 
-// Phase A for one word, bit 4j+q of every produced word <-> site q*8+j:
+// the same with 16 bits (k_pack2, k_presence: 4 slots) per row
+__device__ __forceinline__ void word_load16(__amdgpu_buffer_rsrc_t rsrc, int b0, int RS, int row0, const RowOff &ro, uint32_t d[32]) {
+    const int v0 = b0 + row0 * RS, v1 = v0 + 16 * RS;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) d[s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, v0, ro.v[s], 0);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) d[16 + s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, v1, ro.v[s], 0);
+}
+
+// two rows' 16-bit pieces (4 slots each) -> byte k = slot k of row 0 | slot k of row 1 << 4
+__device__ __forceinline__ uint32_t merge16(uint32_t x0, uint32_t x1) { return pg_nib_expand4(x0) | (pg_nib_expand4(x1) << 4); }
+
+// Phase A for one word (d: word_load16), bit 4j+q of every produced word <-> site q*8+j:
 //   v[k]  = called bits of haplotype h0+k,   pa[a] = sites at which allele a occurs among this lane's four haplotypes.
 __device__ __forceinline__ void word_called_presence(const uint32_t d[32], uint32_t v[4], uint32_t pa[4]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const uint32_t *e = d + 8 * q;
         uint32_t r[4];
-        btrans4(e[0] | (e[1] << 4), e[2] | (e[3] << 4), e[4] | (e[5] << 4), e[6] | (e[7] << 4), r);
+        btrans4(merge16(e[0], e[1]), merge16(e[2], e[3]), merge16(e[4], e[5]), merge16(e[6], e[7]), r);
         const uint32_t o = r[0] | r[1] | r[2] | r[3];                    // 8 sites x presence nibble
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -120,7 +133,7 @@ __device__ __forceinline__ void word_called_presence(const uint32_t d[32], uint3
 // hold a row beyond the descriptor and read as zero.  SA[a]: entries (bits, in output order) whose tested allele is a (A, C or
 // G: the highest allele present is never tested); SE[a]: entries that exclude allele a (A or C).
 //   x[0][k] = x, x[1][k] = v of haplotype h0+k over the 32 listed virtual sites.
-__device__ __forceinline__ void poly_word(__amdgpu_buffer_rsrc_t rsrc, int h0, int S, uint32_t vlist, const uint32_t SA[3],
+__device__ __forceinline__ void poly_word(__amdgpu_buffer_rsrc_t rsrc, int h0, int RS, uint32_t vlist, const uint32_t SA[3],
                                           const uint32_t SE[2], uint32_t x[PG_XV_PLANES][4]) {
     uint32_t al[4][4];                                                   // [allele][haplotype]: carries the allele
 #pragma unroll
@@ -129,10 +142,10 @@ __device__ __forceinline__ void poly_word(__amdgpu_buffer_rsrc_t rsrc, int h0, i
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             const int row = __builtin_amdgcn_readlane((int)vlist, q * 8 + s) & 0xffff;
-            d[s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rsrc, h0, row * S, 0);
+            d[s] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(rsrc, h0 >> 1, row * RS, 0);
         }
         uint32_t r[4];
-        btrans4(d[0] | (d[1] << 4), d[2] | (d[3] << 4), d[4] | (d[5] << 4), d[6] | (d[7] << 4), r);
+        btrans4(merge16(d[0], d[1]), merge16(d[2], d[3]), merge16(d[4], d[5]), merge16(d[6], d[7]), r);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -177,13 +190,13 @@ __device__ __forceinline__ uint32_t tri_mask(const uint32_t p[4]) {
 }
 __device__ __forceinline__ uint32_t quad_mask(const uint32_t p[4]) { return p[0] & p[1] & p[2] & p[3]; }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t group_rsrc(const int8_t *gt, int S, int64_t first_row, int nrows) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(gt + first_row * (int64_t)S), 0, nrows * S, 0x00020000);
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t group_rsrc(const int8_t *gt, int RS, int64_t first_row, int nrows) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(gt + first_row * (int64_t)RS), 0, nrows * RS, 0x00020000);
 }
 
 // More than 1024 haplotype slots do not fit one block: k_presence (phase A only, grid.z = blocks of 1024 slots) first ORs the
 // presence nibbles of all slot blocks into pres[word][4]; k_pack2<.,.,PRES=1> then reads them.
-__global__ __launch_bounds__(256) void k_presence(const int8_t *__restrict__ gt, int S, const int64_t *__restrict__ win_lo,
+__global__ __launch_bounds__(256) void k_presence(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
                                                   const int64_t *__restrict__ win_hi, const int64_t *__restrict__ goff,
                                                   uint32_t *__restrict__ pres, int grp) {
     const int b = blockIdx.y, g = blockIdx.x;
@@ -195,14 +208,14 @@ __global__ __launch_bounds__(256) void k_presence(const int8_t *__restrict__ gt,
     const int h0 = 4 * (blockIdx.z * 256 + threadIdx.x);
     const int64_t first = lo + 32ll * w_begin;
     const int nrows = (int)((hi - first) < 32ll * grp ? (hi - first) : 32ll * grp);
-    const __amdgpu_buffer_rsrc_t rsrc = group_rsrc(gt, S, first, nrows);
+    const __amdgpu_buffer_rsrc_t rsrc = group_rsrc(gt, RS, first, nrows);
     uint32_t *dst = pres + (size_t)(goff[b] + g) * grp * 4u;
-    const RowOff ro = make_row_off(S);
+    const RowOff ro = make_row_off(RS);
     for (int w = w_begin; w < w_end; ++w) {
         uint32_t v[4], pa[4] = {0u, 0u, 0u, 0u};
-        if (h0 < S) {
+        if (h0 < 2 * RS) {
             uint32_t d[32];
-            word_load(rsrc, h0, S, (w - w_begin) * 32, ro, d);
+            word_load16(rsrc, h0 >> 1, RS, (w - w_begin) * 32, ro, d);
             word_called_presence(d, v, pa);
         }
         wave_or4(pa);
@@ -255,7 +268,7 @@ __global__ __launch_bounds__(256) void k_word_scan(const int64_t *__restrict__ w
 }
 
 template <int TPB, int DIP, int PRES>
-__global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, int S, const int64_t *__restrict__ win_lo,
+__global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
                                                const int64_t *__restrict__ win_hi, const int64_t *__restrict__ goff,
                                                const int64_t *__restrict__ vgoff, uint32_t *__restrict__ Vp, int NPv,
                                                uint32_t *__restrict__ XV, int NP, int32_t *__restrict__ nw,
@@ -273,13 +286,13 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
     const int t = blockIdx.z * TPB + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int h0 = 4 * t;
-    // pad threads (h0 >= S = round_up(n_hap, 16)) neither load nor store: the pair kernels read pad units / haplotypes only as rows
-    // of their last 8- / 16-row task (all below S) and discard those rows
-    const bool has_data = h0 < S;
+    // pad threads (h0 >= 2 * RS = round_up(n_hap, 16)) neither load nor store: the pair kernels read pad units / haplotypes only as
+    // rows of their last 8- / 16-row task (all below 2 * RS) and discard those rows
+    const bool has_data = h0 < 2 * RS;
     const int u0 = DIP ? 2 * t : h0;         // first unit of the called plane owned by this thread
     const int64_t first = lo + 32ll * w_begin;
     const int nrows = (int)((hi - first) < 32ll * grp ? (hi - first) : 32ll * grp);
-    const __amdgpu_buffer_rsrc_t rsrc = group_rsrc(gt, S, first, nrows);
+    const __amdgpu_buffer_rsrc_t rsrc = group_rsrc(gt, RS, first, nrows);
     uint32_t vlist = (uint32_t)nrows;        // lane i = list entry i; "nrows" is one row past the descriptor: reads as zero
     int cnt = 0, nflush = 0, parity = 0;
     uint32_t bad = 0u;
@@ -331,7 +344,7 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
             if (threadIdx.x == 0) atomicOr(mismatch, 2);
         } else if (has_data) {
             uint32_t x[PG_XV_PLANES][4];
-            poly_word(rsrc, h0, S, vlist, SA, SE, x);
+            poly_word(rsrc, h0, RS, vlist, SA, SE, x);
             uint32_t *o = xv_base + (size_t)slot * PG_XV_PLANES * (size_t)NP + 2 * h0;
             store16(o, x[0][0], x[1][0], x[0][1], x[1][1]);
             store16(o + 4, x[0][2], x[1][2], x[0][3], x[1][3]);
@@ -343,8 +356,8 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
     uint32_t dn[32];
 #pragma unroll
     for (int s = 0; s < 32; ++s) dn[s] = 0u;
-    const RowOff ro = make_row_off(S);
-    if (has_data) word_load(rsrc, h0, S, 0, ro, dn);
+    const RowOff ro = make_row_off(RS);
+    if (has_data) word_load16(rsrc, h0 >> 1, RS, 0, ro, dn);
     for (int wq = 0; 4 * wq + w_begin < w_end; ++wq) {
         uint32_t vhold[4][4];
 #pragma unroll
@@ -355,7 +368,7 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
             uint32_t d[32];
 #pragma unroll
             for (int s = 0; s < 32; ++s) d[s] = dn[s];
-            if (has_data) word_load(rsrc, h0, S, (w + 1 - w_begin) * 32, ro, dn);
+            if (has_data) word_load16(rsrc, h0 >> 1, RS, (w + 1 - w_begin) * 32, ro, dn);
             if (live && has_data) word_called_presence(d, v, pa);
 #pragma unroll
             for (int k = 0; k < 4; ++k) vhold[k][k4] = v[k];
@@ -441,20 +454,34 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
 // every row exactly once (k_pack2 fetched the ~11 % polymorphic rows of typical data a second time, PMC FETCH_SIZE).
 // The entries of a word are appended q-major (sites q*8+j share r[q]): the bit order inside an XV word is arbitrary as
 // long as it is the same for every haplotype and both planes.
+//
+// A lane covers 8 slots = one dword of a resident row (two slots per byte, pg_nib.h): a pair of row dwords (d0, d1) splits into
+// the merged dwords k_pack2 builds from int8 rows -- even slots bfi(0xF0F0F0F0, d1 << 4, d0), odd slots bfi(0xF0F0F0F0, d1,
+// d0 >> 4) --, so that the byte transposition and everything after it run unchanged on both halves; R[q][k] / v[k] belong to
+// slot h0 + k.
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void word_called_presence_keep(const uint32_t d[32], uint32_t v[4], uint32_t pa[4], uint32_t R[4][4]) {
+__device__ __forceinline__ uint32_t bfi_f0(uint32_t hi, uint32_t lo) { return (hi & 0xF0F0F0F0u) | (lo & 0x0F0F0F0Fu); }
+
+__device__ __forceinline__ void word_called_presence_keep(const uint32_t d[32], uint32_t v[8], uint32_t pa[4], uint32_t R[4][8]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const uint32_t *e = d + 8 * q;
-        btrans4(e[0] | (e[1] << 4), e[2] | (e[3] << 4), e[4] | (e[5] << 4), e[6] | (e[7] << 4), R[q]);
-        const uint32_t o = R[q][0] | R[q][1] | R[q][2] | R[q][3];          // 8 sites x presence nibble
+        uint32_t re[4], ro[4];
+        btrans4(bfi_f0(e[1] << 4, e[0]), bfi_f0(e[3] << 4, e[2]), bfi_f0(e[5] << 4, e[4]), bfi_f0(e[7] << 4, e[6]), re);
+        btrans4(bfi_f0(e[1], e[0] >> 4), bfi_f0(e[3], e[2] >> 4), bfi_f0(e[5], e[4] >> 4), bfi_f0(e[7], e[6] >> 4), ro);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            R[q][2 * k] = re[k];
+            R[q][2 * k + 1] = ro[k];
+        }
+        const uint32_t o = (re[0] | re[1] | re[2] | re[3]) | (ro[0] | ro[1] | ro[2] | ro[3]);      // 8 sites x presence nibble
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             const uint32_t piece = (a >= q ? (o >> (a - q)) : (o << (q - a))) & (0x11111111u << q);
             pa[a] = q ? (pa[a] | piece) : piece;
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < 8; ++k) {
             // called = nibble != 0 = bit 3 of (nibble + 7); moved to bit q of the nibble
             const uint32_t t = R[q][k] + 0x77777777u;
             const uint32_t c = (q == 3 ? t : (t >> (3 - q))) & (0x11111111u << q);
@@ -468,16 +495,16 @@ __device__ __forceinline__ void word_called_presence_keep(const uint32_t d[32], 
 // burst costs the HBM fewer read <-> write turn-arounds than the same bytes trickling out between the row loads
 // (tools/ubench/pack_rw.hip: - 4.5 % on the kernel's bare traffic; the kernel's time does not depend on the waves per CU down to
 // three blocks, so the 48 KB of LDS cost nothing).  Blocks of one or two waves only (LDS).
-constexpr int PACK_CELLS = 24;                       // uint4 LDS cells per thread (48 KB per two-wave block: three blocks per CU)
+constexpr int PACK_CELLS = 24;                       // uint4 LDS cells per thread (24 KB per one-wave block: six blocks per CU)
 template <int TPB, int DIP, int BURST>
-__global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, int S, const int64_t *__restrict__ win_lo,
+__global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
                                                const int64_t *__restrict__ win_hi, const int64_t *__restrict__ goff,
                                                const int64_t *__restrict__ vgoff, uint32_t *__restrict__ Vp, int NPv,
                                                uint32_t *__restrict__ XV, int NP, int32_t *__restrict__ nw,
                                                int32_t *__restrict__ mismatch, int capg, int grp, int fq, int perm) {
     constexpr int NWAVE = TPB / 64;
-    constexpr int VN = DIP ? 2 : 4;                      // uint4 of called plane per thread and word quadruple
-    const int FQ = fq, xc = (PACK_CELLS - fq * VN) / 2;  // quadruples per burst of the called plane; virtual-site words per burst  // quadruples per burst of the called plane; virtual-site words per burst
+    constexpr int VN = DIP ? 4 : 8;                      // uint4 of called plane per thread and word quadruple
+    const int FQ = fq, xc = (PACK_CELLS - fq * VN) / 4;  // quadruples per burst of the called plane; virtual-site words per burst
     __shared__ uint32_t sh_pres[2][NWAVE][4];
     __shared__ int sh_slot;
     __shared__ uint4 stage[BURST ? PACK_CELLS * TPB : 1];
@@ -494,15 +521,17 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
     const int w_end = (w_begin + grp < W) ? w_begin + grp : W;
     const int t = threadIdx.x;
     const int lane = threadIdx.x & 63;
-    const int h0 = 4 * t;
-    const bool has_data = h0 < S;
-    const int u0 = DIP ? 2 * t : h0;
+    const int h0 = 8 * t;                    // first slot of this thread; its row dword starts at byte 4 * t
+    const bool has_data = h0 < 2 * RS;
+    const int u0 = DIP ? 4 * t : h0;
     const int64_t first = lo + 32ll * w_begin;
     const int nrows = (int)((hi - first) < 32ll * grp ? (hi - first) : 32ll * grp);
-    const __amdgpu_buffer_rsrc_t rsrc = group_rsrc(gt, S, first, nrows);
+    const __amdgpu_buffer_rsrc_t rsrc = group_rsrc(gt, RS, first, nrows);
     int cnt = 0, parity = 0;                 // cnt: entries of the pending output word (uniform, 0..31)
     uint32_t MA = 0u, ME = 0u;               // nibble masks of the pending 8-entry dword (uniform)
-    uint32_t cur[4] = {0u, 0u, 0u, 0u}, xo[4] = {0u, 0u, 0u, 0u}, vo[4] = {0u, 0u, 0u, 0u};
+    uint32_t cur[8], xo[8], vo[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cur[k] = xo[k] = vo[k] = 0u;
     uint32_t bad = 0u;
     uint32_t *xv_base = XV + (size_t)goff[b] * capg * PG_XV_PLANES * (size_t)NP;
     const int capw = (int)(goff[b + 1] - goff[b]) * capg;          // words reserved for this window
@@ -529,8 +558,8 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
                 if (threadIdx.x == 0) atomicOr(mismatch, 2);
             } else if (has_data) {
                 uint4 *o = reinterpret_cast<uint4 *>(xv_base + (size_t)(slot0 + k) * PG_XV_PLANES * (size_t)NP + 2 * h0);
-                o[0] = stage_x[(2 * k) * TPB + t];
-                o[1] = stage_x[(2 * k + 1) * TPB + t];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = stage_x[(4 * k + i) * TPB + t];
             }
         }
         nxs = 0;
@@ -538,8 +567,8 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
     auto store_word = [&]() {                // the pending planes become one dense word of XV (the window's next free word)
         if (BURST) {
             if (has_data) {
-                stage_x[(2 * nxs) * TPB + t] = make_uint4(xo[0], vo[0], xo[1], vo[1]);
-                stage_x[(2 * nxs + 1) * TPB + t] = make_uint4(xo[2], vo[2], xo[3], vo[3]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) stage_x[(4 * nxs + i) * TPB + t] = make_uint4(xo[2 * i], vo[2 * i], xo[2 * i + 1], vo[2 * i + 1]);
             }
             if (++nxs == xc) flush_x();
         } else {
@@ -548,12 +577,12 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
                 if (threadIdx.x == 0) atomicOr(mismatch, 2);
             } else if (has_data) {
                 uint32_t *o = xv_base + (size_t)slot * PG_XV_PLANES * (size_t)NP + 2 * h0;
-                store16(o, xo[0], vo[0], xo[1], vo[1]);
-                store16(o + 4, xo[2], vo[2], xo[3], vo[3]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) store16(o + 4 * i, xo[2 * i], vo[2 * i], xo[2 * i + 1], vo[2 * i + 1]);
             }
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) xo[k] = vo[k] = 0u;
+        for (int k = 0; k < 8; ++k) xo[k] = vo[k] = 0u;
     };
     auto flush_v = [&]() {                   // BURST: the staged quadruples of the called plane
         if (has_data)
@@ -567,7 +596,7 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
     auto finish_dword = [&](int qd) {        // 8 entries (nibbles of cur[k]) -> bits 4j+qd of the two planes
         const uint32_t nME = ~ME;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < 8; ++k) {
             const uint32_t cx = (((cur[k] & MA) + 0x77777777u) >> 3) & 0x11111111u;
             const uint32_t cv = (((cur[k] & nME) + 0x77777777u) >> 3) & 0x11111111u;
             xo[k] |= cx << qd;
@@ -577,10 +606,10 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
         MA = 0u;
         ME = 0u;
     };
-    auto append = [&](const uint32_t (&Rq)[4], int j, uint32_t A, uint32_t E) {       // j, A, E uniform
+    auto append = [&](const uint32_t (&Rq)[8], int j, uint32_t A, uint32_t E) {       // j, A, E uniform
         const int sh = 4 * (cnt & 7);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) cur[k] |= __builtin_amdgcn_ubfe(Rq[k], 4 * j, 4) << sh;
+        for (int k = 0; k < 8; ++k) cur[k] |= __builtin_amdgcn_ubfe(Rq[k], 4 * j, 4) << sh;
         MA |= A << sh;
         ME |= E << sh;
         ++cnt;
@@ -595,28 +624,28 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
     uint32_t dn[32];
 #pragma unroll
     for (int s = 0; s < 32; ++s) dn[s] = 0u;
-    const RowOff ro = make_row_off(S);
-    if (has_data) word_load(rsrc, h0, S, 0, ro, dn);
+    const RowOff ro = make_row_off(RS);
+    if (has_data) word_load(rsrc, 4 * t, RS, 0, ro, dn);
     for (int wq = 0; 4 * wq + w_begin < w_end; ++wq) {
-        uint32_t vhold[4][4];
+        uint32_t vhold[8][4];
 #pragma unroll
         for (int k4 = 0; k4 < 4; ++k4) {
             const int w = w_begin + 4 * wq + k4;
-            uint32_t v[4] = {0u, 0u, 0u, 0u}, pa[4] = {0u, 0u, 0u, 0u};
-            uint32_t R[4][4];
+            uint32_t v[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, pa[4] = {0u, 0u, 0u, 0u};
+            uint32_t R[4][8];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) R[q][k] = 0u;
+                for (int k = 0; k < 8; ++k) R[q][k] = 0u;
             const bool live = w < w_end;            // block-uniform
             uint32_t d[32];
 #pragma unroll
             for (int s = 0; s < 32; ++s) d[s] = dn[s];
-            if (has_data) word_load(rsrc, h0, S, (w + 1 - w_begin) * 32, ro, dn);
+            if (has_data) word_load(rsrc, 4 * t, RS, (w + 1 - w_begin) * 32, ro, dn);
             if (live && has_data) word_called_presence_keep(d, v, pa, R);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) vhold[k][k4] = v[k];
-            if (DIP) bad |= (v[0] ^ v[1]) | (v[2] ^ v[3]);
+            for (int k = 0; k < 8; ++k) vhold[k][k4] = v[k];
+            if (DIP) bad |= (v[0] ^ v[1]) | (v[2] ^ v[3]) | (v[4] ^ v[5]) | (v[6] ^ v[7]);      // individual = byte: even ^ odd slot
             if (live) {
                 uint32_t pr[4];
 #pragma unroll
@@ -682,23 +711,20 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
         if (BURST) {
             if (nq == 0) wq_first = wq;
             if (has_data) {
-                if (DIP) {
-                    stage_v[(nq * VN) * TPB + t] = make_uint4(vhold[0][0], vhold[0][1], vhold[0][2], vhold[0][3]);
-                    stage_v[(nq * VN + 1) * TPB + t] = make_uint4(vhold[2][0], vhold[2][1], vhold[2][2], vhold[2][3]);
-                } else {
+                // (DIP: unit = individual 4t + k = slots h0 + 2k, h0 + 2k + 1, whose called planes agree unless `bad`)
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) stage_v[(nq * VN + k) * TPB + t] = make_uint4(vhold[k][0], vhold[k][1], vhold[k][2], vhold[k][3]);
+                for (int k = 0; k < VN; ++k) {
+                    const int hk = DIP ? 2 * k : k;
+                    stage_v[(nq * VN + k) * TPB + t] = make_uint4(vhold[hk][0], vhold[hk][1], vhold[hk][2], vhold[hk][3]);
                 }
             }
             if (++nq == FQ) flush_v();
         } else if (has_data) {
             uint32_t *o = Vp + ((size_t)(vg_base + wq) * NPv + u0) * 4u;
-            if (DIP) {
-                store16(o, vhold[0][0], vhold[0][1], vhold[0][2], vhold[0][3]);
-                store16(o + 4, vhold[2][0], vhold[2][1], vhold[2][2], vhold[2][3]);
-            } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) store16(o + 4 * k, vhold[k][0], vhold[k][1], vhold[k][2], vhold[k][3]);
+            for (int k = 0; k < VN; ++k) {
+                const int hk = DIP ? 2 * k : k;
+                store16(o + 4 * k, vhold[hk][0], vhold[hk][1], vhold[hk][2], vhold[hk][3]);
             }
         }
     }
@@ -712,7 +738,7 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
 }
 
 template <int DIP>
-static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *gt, int S, const int64_t *win_lo,
+static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *gt, int RS, const int64_t *win_lo,
                          const int64_t *win_hi, const int64_t *goff, const int64_t *vgoff, uint32_t *Vp, int NPv, uint32_t *XV,
                          int NP, int32_t *nw, int32_t *mismatch, uint32_t *pres, int capg, int grp) {
     // Up to 4096 slots: k_pack3 (one block of up to 16 waves per group; every row fetched once; PMC: 2.27 instead of 2.56 GB per C2 pass, 44.5 instead of 49.2 GB per
@@ -721,12 +747,14 @@ static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *g
     // k_pack3 lost on two-wave blocks, 8.3-9.0 ms: every wave of a block runs the per-entry scalar loop).  More than 4096 slots:
     // k_pack2 behind the presence pre-pass (round 2 took that route from 1024 slots on: C4 read its rows twice, 0.27 of HBM).
     // PG_PACK2=1 forces k_pack2 (A/B runs and tests).
+    // (k_pack3: a lane covers 8 slots = one dword of a resident row, threads / 2 lanes; k_pack2: 4 slots, `threads`)
     const bool force2 = getenv("PG_PACK2") != nullptr;
     if (threads <= 1024 && !force2) {
-#define PG_PACK3B(T, B) hipLaunchKernelGGL((k_pack3<T, DIP, B>), grid, dim3(T), 0, st, gt, S, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, capg, grp, fq, perm)
+        const int lanes = (threads + 1) / 2;
+#define PG_PACK3B(T, B) hipLaunchKernelGGL((k_pack3<T, DIP, B>), grid, dim3(T), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, capg, grp, fq, perm)
 #define PG_PACK3(T) PG_PACK3B(T, 0)
-        // quadruples of the called plane per burst (the rest of the 24 LDS cells per thread holds virtual-site words)
-        const int fq = DIP ? 8 : 4;
+        // quadruples of the called plane per burst (the rest of the 24 LDS cells per thread holds virtual-site words: two)
+        const int fq = DIP ? 4 : 2;
         // PG_PACK_PERM=k (experiment): windows in the order 0, P, 2P, ... (mod n), P the number coprime with n next to n / k
         int perm = 1;
         if (const char *pe = getenv("PG_PACK_PERM")) {
@@ -738,28 +766,27 @@ static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *g
             }
         }
         const bool burst = getenv("PG_PACK_BURST") == nullptr || atoi(getenv("PG_PACK_BURST")) != 0;       // (0: A/B runs, tests)
-        if (threads <= 64 && burst) PG_PACK3B(64, 1);
-        else if (threads <= 128 && burst) PG_PACK3B(128, 1);
-        else if (threads <= 64) PG_PACK3(64);
-        else if (threads <= 128) PG_PACK3(128);
-        else if (threads <= 256) PG_PACK3(256);
-        else if (threads <= 512) PG_PACK3(512);            // up to 2048 slots (C4: 2000 haplotypes): eight waves meet in LDS per word
-        else PG_PACK3(1024);                               // up to 4096 slots
+        if (lanes <= 64 && burst) PG_PACK3B(64, 1);        // up to 512 slots (the north star: 400 haplotypes, 50 lanes)
+        else if (lanes <= 128 && burst) PG_PACK3B(128, 1);
+        else if (lanes <= 64) PG_PACK3(64);
+        else if (lanes <= 128) PG_PACK3(128);
+        else if (lanes <= 256) PG_PACK3(256);              // up to 2048 slots (C4: 2000 haplotypes): four waves meet in LDS per word
+        else PG_PACK3(512);                                // up to 4096 slots
 #undef PG_PACK3
 #undef PG_PACK3B
         return;
     }
     if (threads <= 64)
-        hipLaunchKernelGGL((k_pack2<64, DIP, 0>), grid, dim3(64), 0, st, gt, S, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
+        hipLaunchKernelGGL((k_pack2<64, DIP, 0>), grid, dim3(64), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
     else if (threads <= 128)
-        hipLaunchKernelGGL((k_pack2<128, DIP, 0>), grid, dim3(128), 0, st, gt, S, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
+        hipLaunchKernelGGL((k_pack2<128, DIP, 0>), grid, dim3(128), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
     else if (threads <= 256)
-        hipLaunchKernelGGL((k_pack2<256, DIP, 0>), grid, dim3(256), 0, st, gt, S, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
+        hipLaunchKernelGGL((k_pack2<256, DIP, 0>), grid, dim3(256), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
     else {
         grid.z = (threads + 255) / 256;
-        hipLaunchKernelGGL(k_presence, grid, dim3(256), 0, st, gt, S, win_lo, win_hi, goff, pres, grp);
+        hipLaunchKernelGGL(k_presence, grid, dim3(256), 0, st, gt, RS, win_lo, win_hi, goff, pres, grp);
         hipLaunchKernelGGL(k_word_scan, dim3(grid.y), dim3(256), 0, st, win_lo, win_hi, goff, pres, nw, grp);
-        hipLaunchKernelGGL((k_pack2<256, DIP, 1>), grid, dim3(256), 0, st, gt, S, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
+        hipLaunchKernelGGL((k_pack2<256, DIP, 1>), grid, dim3(256), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
     }
 }
 
@@ -767,7 +794,7 @@ static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *g
 bool pg_pack_needs_presence(int NP) { return NP / 4 > 1024 || (getenv("PG_PACK2") != nullptr && NP / 4 > 256); }
 
 // pres: scratch of total_groups * PG_GROUP * 4 words, only used (and zeroed here) in that mode
-void pg_launch_pack2(hipStream_t st, const int8_t *gt, int S, const int64_t *win_lo, const int64_t *win_hi,
+void pg_launch_pack2(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi,
                      const int64_t *goff, const int64_t *vgoff, int n_win, int max_groups, int64_t total_groups, uint32_t *Vp,
                      int NPv, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch, uint32_t *pres, int capg, int grp) {
     // nw[0 .. n_win): the caller hands over zeroed per-window word counters (atomic allocation; k_pairD reads them even when
@@ -776,8 +803,8 @@ void pg_launch_pack2(hipStream_t st, const int8_t *gt, int S, const int64_t *win
     const int threads = NP / 4;
     if (pg_pack_needs_presence(NP)) (void)hipMemsetAsync(pres, 0, (size_t)total_groups * grp * 16u, st);
     dim3 grid(max_groups, n_win);
-    if (dip) launch_pack2<1>(st, threads, grid, gt, S, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
-    else launch_pack2<0>(st, threads, grid, gt, S, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
+    if (dip) launch_pack2<1>(st, threads, grid, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
+    else launch_pack2<0>(st, threads, grid, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -415,9 +415,14 @@ __global__ __launch_bounds__(256) void k_tok_cells(const uint8_t *__restrict__ t
                 }
             }
         }
-        // (LDS operations of a wavefront execute in order: the reads below see the bytes scattered above)
-        uint32_t *grow = reinterpret_cast<uint32_t *>(rows + row * (int64_t)S);
-        for (int k = lane; k < S / 4; k += 64) grow[k] = reinterpret_cast<const uint32_t *>(lrow)[k];
+        // (LDS operations of a wavefront execute in order: the reads below see the bytes scattered above); the resident row holds
+        // two slots per byte (pg_nib.h): a lane packs 8 slots into one dword of it
+        uint32_t *grow = reinterpret_cast<uint32_t *>(rows + row * (int64_t)(S >> 1));
+        const uint2 *lrow2 = reinterpret_cast<const uint2 *>(lrow);
+        for (int k = lane; k < S / 8; k += 64) {
+            const uint2 w = lrow2[k];
+            grow[k] = pg_nib_pack4(w.x) | (pg_nib_pack4(w.y) << 16);
+        }
     }
     if (bad) atomicOr(status, bad);
 }
@@ -468,7 +473,7 @@ __global__ __launch_bounds__(256) void k_tok_cells3(const uint8_t *__restrict__ 
     long long cav = -1;
     if (lane < n_here) cav = cells_at_in[row0 + lane];
     const int ca_lo = (int)(uint32_t)cav, ca_hi = (int)(cav >> 32);
-    const int n_it = (n_cols + 63) >> 6, n_dw = S >> 2, n_dwit = (n_dw + 63) >> 6;
+    const int n_it = (n_cols + 63) >> 6, n_dw = S >> 2, n_dwit = (n_dw + 63) >> 6, n_gdw = S >> 3, n_gdwit = (n_gdw + 63) >> 6;
     const int dump = S + lane;
     uint32_t badv = 0u;
     int4 ev[NIT > 0 ? NIT : 1];
@@ -545,11 +550,14 @@ __global__ __launch_bounds__(256) void k_tok_cells3(const uint8_t *__restrict__ 
                 }
             }
         }
-        // (LDS operations of a wavefront execute in order: the reads below see the bytes scattered above)
-        uint32_t *grow = reinterpret_cast<uint32_t *>(rows + row * (int64_t)S);
-        for (int j = 0; j < n_dwit; ++j) {
-            const int k0 = lane + 64 * j, k = k0 < n_dw ? k0 : n_dw - 1;
-            grow[k] = reinterpret_cast<const uint32_t *>(lrow)[k];
+        // (LDS operations of a wavefront execute in order: the reads below see the bytes scattered above); the resident row holds
+        // two slots per byte (pg_nib.h): a lane packs 8 slots into one dword of it
+        uint32_t *grow = reinterpret_cast<uint32_t *>(rows + row * (int64_t)(S >> 1));
+        const uint2 *lrow2 = reinterpret_cast<const uint2 *>(lrow);
+        for (int j = 0; j < n_gdwit; ++j) {
+            const int k0 = lane + 64 * j, k = k0 < n_gdw ? k0 : n_gdw - 1;
+            const uint2 w = lrow2[k];
+            grow[k] = pg_nib_pack4(w.x) | (pg_nib_pack4(w.y) << 16);
         }
     }
     if (__ballot(badv != 0u) && lane == 0) atomicOr(status, TOK_IRREGULAR);
@@ -976,7 +984,12 @@ static int tok_parse(pg_ctx *c, int slot, int64_t row_offset, int64_t row_capaci
     const size_t tab_bytes = (size_t)n_cols * (max_ploidy + 3) * 4, lds_bytes = tab_bytes + 4 * (size_t)c->S;
     static const bool first_form = getenv("PG_TOK_PARSE") && atoi(getenv("PG_TOK_PARSE")) == 1;
     const bool second_form = lds_bytes <= 60 * 1024 && !first_form;
-    if (!second_form) HIPCHK(hipMemsetAsync(c->gt.p + row_offset * c->S, 0, (size_t)n_lines * c->S, st));
+    // (the first form scatters int8 slots straight to global memory: into a cleared int8 block of its own, which k_nib_pack then
+    // turns into resident rows -- no two lanes ever share a byte of a resident row)
+    if (!second_form) {
+        if ((rc = T.rows8.ensure_roomy((size_t)n_lines * c->S)) != PG_OK) return rc;
+        HIPCHK(hipMemsetAsync(T.rows8.p, 0, (size_t)n_lines * c->S, st));
+    }
     DipTable dip;
     memset(dip.v, 0, sizeof(dip.v));
     {
@@ -1011,7 +1024,7 @@ static int tok_parse(pg_ctx *c, int slot, int64_t row_offset, int64_t row_capaci
         static const bool general_cells = getenv("PG_TOK_PARSE") && atoi(getenv("PG_TOK_PARSE")) == 2;      // (A/B, tests)
         if (widest <= 3 && lds3 <= 60 * 1024 && !general_cells) {
 #define PG_CELLS3N(F, N) hipLaunchKernelGGL((k_tok_cells3<F, N>), grid, dim3(256), lds3, st, T.tp, T.cells_at.p, n_lines, n_cols, max_ploidy, T.dcols.p, \
-                                            c->gt.p + row_offset * c->S, c->S, d_status, dip)
+                                            c->gt.p + row_offset * c->RS, c->S, d_status, dip)
             // (a lane's column-table entries in registers for layouts of up to 256 columns; PG_TOK_CELLS_REGS=0: the table read per step)
             static const bool in_regs = !(getenv("PG_TOK_CELLS_REGS") && atoi(getenv("PG_TOK_CELLS_REGS")) == 0);
             const int nit = (n_cols + 63) / 64;
@@ -1030,14 +1043,15 @@ static int tok_parse(pg_ctx *c, int slot, int64_t row_offset, int64_t row_capaci
 #undef PG_CELLS3N
         } else {
             hipLaunchKernelGGL(k_tok_cells, grid, dim3(256), lds_bytes, st, T.tp, T.cells_at.p,
-                               n_lines, T.fmt, n_cols, max_ploidy, T.dcols.p, c->gt.p + row_offset * c->S, c->S, d_status, dip);
+                               n_lines, T.fmt, n_cols, max_ploidy, T.dcols.p, c->gt.p + row_offset * c->RS, c->S, d_status, dip);
         }
     } else {
         hipLaunchKernelGGL(k_tok_parse, dim3((unsigned)((n_lines + 3) / 4)), dim3(256), 0, st, T.tp, T.nl.p, n_lines, T.fmt, n_cols,
                            T.cells_w, max_ploidy, T.dcols.p, T.dcols.p + (size_t)n_cols * max_ploidy,
                            T.dcols.p + (size_t)n_cols * (max_ploidy + 1), T.dcols.p + (size_t)n_cols * (max_ploidy + 2),
-                           c->gt.p + row_offset * c->S, c->S,
+                           T.rows8.p, c->S,
                            T.pos64.p, T.off.p, T.off.p + run_cap, T.pos.p, d_status + 1, run_cap, d_status, dip);
+        pg_launch_nib_pack(st, T.rows8.p, c->S, c->n_hap, n_lines, c->gt.p + row_offset * c->RS, c->RS);
     }
     HIPCHK(hipGetLastError());
     if (T.deflated && T.inf.crc_pending) {
@@ -1374,7 +1388,7 @@ extern "C" int pg_unpack_staged(pg_ctx *c, int slot, int64_t src_offset, int64_t
     HIPCHK(hipStreamSynchronize(c->stream_up));                  // (the table of an earlier call may still be on its way)
     memcpy(T.h_cols.p, slot_src, (size_t)c->n_hap * 4);
     HIPCHK(hipMemcpyAsync(T.dcols.p, T.h_cols.p, (size_t)c->n_hap * 4, hipMemcpyHostToDevice, c->stream_up));
-    pg_launch_unpack(c->stream_up, T.text.p + src_offset, n_cols, n_rows, T.dcols.p, c->n_hap, c->gt.p + row_offset * c->S, c->S);
+    pg_launch_unpack(c->stream_up, T.text.p + src_offset, n_cols, n_rows, T.dcols.p, c->n_hap, c->gt.p + row_offset * c->RS, c->RS);
     HIPCHK(hipGetLastError());
     return PG_OK;
 }
