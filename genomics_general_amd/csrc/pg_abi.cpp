@@ -810,7 +810,9 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
     }
     // scratch bytes per 32-site input word of one slot: called plane + reserved virtual-site planes (capg words per group)
     const int capg = c->xv_worst ? PG_XV_CAP(grp) : PG_XV_CAP_DEFAULT(grp);
-    const int64_t word_bytes = ((int64_t)NP * 4 * PG_XV_PLANES * capg + grp - 1) / grp + (int64_t)NPv * 4;
+    // the fused form of the pack kernel counts the called pairs itself: no called plane, no C-count kernel (pg_pair2.hip)
+    const bool fused = pg_pack_fuse_fits(NP, NPv, n_units, n_win);
+    const int64_t word_bytes = ((int64_t)NP * 4 * PG_XV_PLANES * capg + grp - 1) / grp + (fused ? 0 : (int64_t)NPv * 4);
     // sub-batch size: at most half the scratch budget per slot (and, for the two-stream pipeline, at least ~8 sub-batches per
     // call, but none so small that it cannot fill the GPU)
     int64_t total_words_all = 0;
@@ -867,10 +869,13 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
         int64_t *h = sl.host.p;
         int64_t ga = 0, va = 0;
         int max_groups = 0;
+        int64_t max_wds = 0, sum_wds = 0;
         for (int k = 0; k < nb; ++k) {
             h[k] = lo[w0 + k];
             h[nb + k] = hi[w0 + k];
             const int64_t wds = (hi[w0 + k] - lo[w0 + k] + 31) / 32;
+            max_wds = std::max(max_wds, wds);
+            sum_wds += wds;
             h[2 * (size_t)nb + k] = ga;
             h[3 * (size_t)nb + 1 + k] = va;
             const int64_t groups = (wds + grp - 1) / grp;
@@ -886,7 +891,7 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
                       *d_vgoff = sl.win.p + 3 * (size_t)nb + 1;
         int32_t *d_nw = reinterpret_cast<int32_t *>(sl.win.p + 4 * (size_t)nb + 2);
         // + 4 word groups / words: the last stage (look-ahead load) of the pair kernels reads up to three past a part's range
-        if ((rc = sl.Vp.ensure((size_t)(std::max<int64_t>(va, 1) + 4) * NPv * 4)) != PG_OK) return rc;
+        if (!fused && (rc = sl.Vp.ensure((size_t)(std::max<int64_t>(va, 1) + 4) * NPv * 4)) != PG_OK) return rc;
         if ((rc = sl.XV.ensure(((size_t)std::max<int64_t>(ga, 1) * capg + 4) * PG_XV_PLANES * NP)) != PG_OK) return rc;
         if ((rc = c->Cmat.ensure((size_t)nb * n_units * n_units)) != PG_OK) return rc;
         if ((rc = c->Dmat.ensure((size_t)nb * N * N)) != PG_OK) return rc;
@@ -899,8 +904,13 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
             HIPCHK(hipEventRecord(e0, ps));
         }
         if (pg_pack_needs_presence(NP) && (rc = sl.pres.ensure((size_t)std::max<int64_t>(ga, 1) * grp * 4)) != PG_OK) return rc;
-        pg_launch_pack2(ps, c->gt.p, c->RS, d_lo, d_hi, d_goff, d_vgoff, nb, max_groups, ga, sl.Vp.p, NPv, sl.XV.p, NP,
-                        d_nw, dip ? 1 : 0, c->flag.p, sl.pres.p, capg, grp);
+        if (fused) {
+            if (pg_launch_pack_fused(ps, c->gt.p, c->RS, d_lo, d_hi, d_goff, nb, max_wds, sum_wds / nb, sl.XV.p, NP, d_nw, dip ? 1 : 0,
+                                     c->flag.p, capg, n_units, c->Cmat.p))
+                return pg_fail(PG_ERR_HIP, "the fused pack kernel was refused its LDS");
+        } else
+            pg_launch_pack2(ps, c->gt.p, c->RS, d_lo, d_hi, d_goff, d_vgoff, nb, max_groups, ga, sl.Vp.p, NPv, sl.XV.p, NP,
+                            d_nw, dip ? 1 : 0, c->flag.p, sl.pres.p, capg, grp);
         if (time_pack) {
             HIPCHK(hipEventRecord(e1, ps));
             c->events[PG_K_PACK].push_back(std::make_pair(e0, e1));
@@ -909,12 +919,14 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
         HIPCHK(hipEventRecord(sl.packed, ps));
         // ---- stream: pair kernels + consume ----
         if (!single) HIPCHK(hipStreamWaitEvent(c->stream, sl.packed, 0));
-        if ((rc = pg_time_begin(c, PG_K_PAIRWISE, &e0, &e1)) != PG_OK) return rc;
+        if (!fused && (rc = pg_time_begin(c, PG_K_PAIRWISE, &e0, &e1)) != PG_OK) return rc;
         // the pair counts run on the matrix cores (exact products of the bit planes, pg_pair_mfma.hip: MX fp4, or int8 with
         // PG_PAIR_I8=1); PG_PAIR_VALU=1 keeps the popcount kernels (A/B runs, tests)
         const bool valu_pairs = getenv("PG_PAIR_VALU") != nullptr;
         if (valu_pairs && NP % 64) return pg_fail(PG_ERR_STATE, "PG_PAIR_VALU must be set before pg_set_samples (plane stride %d)", NP);
-        if (!valu_pairs && pg_pair_big_fits(NPv, n_units)) {
+        if (fused) {
+            // (C is in Cmat already)
+        } else if (!valu_pairs && pg_pair_big_fits(NPv, n_units)) {
             pg_launch_pairC_big(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, dip ? 1 : 0, va / nb, (int64_t)max_groups * grp * 32, c->Cmat.p);
         } else if (!valu_pairs && pg_pair_tile_fits(NPv)) {
             if (pg_launch_pairC_tile(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, dip ? 1 : 0, va / nb, (int64_t)max_groups * grp * 32, c->Cmat.p))
@@ -922,7 +934,7 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
         } else if (!valu_pairs) pg_launch_pairC_mfma(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, dip ? 1 : 0, va / nb, (int64_t)max_groups * grp * 32, c->Cmat.p);
         else if (dip) pg_launch_pairC(c->stream, sl.Vp.p, d_vgoff, nb, c->tasksC.p, c->n_tasksC, NPv, n_units, 1, va / nb, c->Cmat.p);
         else pg_launch_pairC(c->stream, sl.Vp.p, d_vgoff, nb, c->tasksCh.p, c->n_tasksCh, NPv, n_units, 0, va / nb, c->Cmat.p);
-        if ((rc = pg_time_end(c, PG_K_PAIRWISE, e0, e1, 1)) != PG_OK) return rc;
+        if (!fused && (rc = pg_time_end(c, PG_K_PAIRWISE, e0, e1, 1)) != PG_OK) return rc;
         // (running k_pairD beside k_pairC on a third stream was measured: +3 % throughput, but overlapping kernels make the
         // per-kernel timings ambiguous; kept sequential)
         if ((rc = pg_time_begin(c, PG_K_PAIRD, &e0, &e1)) != PG_OK) return rc;
@@ -979,6 +991,7 @@ static int flag_ready(pg_ctx *c) {
 // with the worst-case reservation.
 static int note_flags(pg_ctx *c, int flag, bool *dip, bool *again) {
     *again = false;
+    if (flag & PG_FLAG_FUSE_STALL) return pg_fail(PG_ERR_STATE, "the fused pack kernel's waves lost each other");
     if (flag & PG_FLAG_XV_OVERFLOW) {
         if (c->xv_worst) return pg_fail(PG_ERR_STATE, "XV overflow with the worst-case reservation");
         c->xv_worst = true;

@@ -29,6 +29,7 @@
 #define PG_NP_MAX_SITES 256
 #define PG_FLAG_MISMATCH 1      // some individual's two haplotypes differ in calledness: the diploid shortcut does not apply
 #define PG_FLAG_XV_OVERFLOW 2   // a window produced more XV words than reserved
+#define PG_FLAG_FUSE_STALL 4    // a wave of the fused pack kernel gave up waiting for the others (never expected: the call fails)
 
 struct PgTask2 {                // one block of k_pairC (8 rows) / k_pairD (16 rows): circulant task, see pair_store_circ
     int32_t row0, nsub, col0, lower;   // rows row0.., columns col0, col0+1, ... (mod n), nsub = number of valid columns; lower = 2
@@ -91,6 +92,17 @@ void pg_launch_pack2(hipStream_t st, const int8_t *gt, int RS, const int64_t *wi
                      const int64_t *goff, const int64_t *vgoff, int n_win, int max_groups, int64_t total_groups, uint32_t *Vp,
                      int NPv, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch, uint32_t *pres, int capg, int grp);
 bool pg_pack_needs_presence(int NP);
+// the fused form of k_pack3: pack and called counts in one kernel, no called plane (pg_pair2.hip); launch: 0 = launched
+struct PgFuseArgs {
+    int32_t n_win, kparts, n_units, T, diag;
+    int32_t *Cmat;
+    signed char a[8][4], b[8][2];           // wave w forms the tiles (a[w][p], b[w][p & 1]), p = 0 .. 3, of those mask[w] names
+    unsigned char mask[8];
+};
+bool pg_pack_fuse_fits(int NP, int NPv, int n_units, int n_win);
+int pg_launch_pack_fused(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi, const int64_t *goff,
+                         int n_win, int64_t max_words, int64_t avg_words, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch,
+                         int capg, int n_units, int32_t *Cmat);
 void pg_launch_expand(hipStream_t st, const int32_t *Cmat, const int32_t *Dmat, int N, int cN, int cshift, int n_win,
                       int32_t *Cfull, int32_t *Dfull);
 void pg_launch_pairC(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, int n_win, const PgTask2 *tasks, int n_tasks,

@@ -29,6 +29,10 @@
 //                                          s_load_dwordx16 per 16 haplotypes, column: one 8-byte load); two padding words at the end
 #include "pg_internal.h"
 
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
 typedef __attribute__((address_space(4))) const uint32_t CU32;
 
 // ------------------------------------------------------------------------------------------------------
@@ -490,18 +494,371 @@ __device__ __forceinline__ void word_called_presence_keep(const uint32_t d[32], 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// The fused form of k_pack3 (FUSE = 1): the called counts C are formed inside the pack kernel and no called plane is written.
+//
+// (R[q][k] + 0x77777777) >> 3 & 0x11111111 -- what word_called_presence_keep squeezes into one bit plane -- is eight sites of slot
+// k as nibbles 0 / 1, i.e. one dword of the MX fp4 fragment of pg_pair_mfma.hip (nibble 0b0001 = 0.5, a product of two called
+// sites 0.25, accumulator = count / 4); the four q of a 32-site word are the 16 bytes that lane (row = unit, K half = word
+// parity) of v_mfma_scale_f32_32x32x64_f8f6f4 reads.  The fragments only have to change lanes, through LDS.
+//
+//   block  = one part of one window (parts below 2^23 sites: the f32 accumulators stay exact; more than one part: integer
+//            atomics into a zeroed Cmat), 8 waves, persistent over the part's words, 8 words = 4 K steps per iteration;
+//   wave   = the one-wave k_pack3 on every eighth word (rows one word ahead, each word behind a descriptor of its own, transposes,
+//            presence, compaction, XV words through nw[b] in bursts of PACK_FUSE_XC from LDS cells of its own), except that the
+//            four nibble dwords of each of its units go into the 16-byte cell frag[iteration % NB][wave][unit] (word_called_
+//            presence_keep's transposes, without the bit squeeze); units from n_units to 32 T and words past the part hold 0;
+//   then   in iteration i + 1 every wave issues its products over the cells of iteration i: four tiles a[p] x b[p & 1] of
+//            PgFuseArgs (tile rows a, tile columns b; pg_fuse_tasks); lane (r, kb) reads the cells [2 s + kb][32 I + r], 512
+//            contiguous bytes per lane half, scales 2^0.
+// The waves meet through two LDS counters per cell slot (written / read by how many waves), polled, not through s_barrier, and
+// the products are pinned between the pieces of the next word's transposes: see the loop.  Measured on the north-star shape
+// (profiles/r08): one __syncthreads() per iteration cost 0.8 ms per pass, the sixteen products of an iteration in a row 0.5 ms.
+// ------------------------------------------------------------------------------------------------------
+constexpr int PACK_FUSE_XC = 2;                      // XV words a wave holds back in LDS (4 uint4 cells per lane and word)
+constexpr int PACK_FUSE_NB = 3;                      // iterations of cells in LDS: a wave may run up to two iterations ahead of the slowest
+constexpr int PACK_FUSE_SPINS = 1 << 22;             // polls of an LDS counter before a wave gives up (PG_FLAG_FUSE_STALL)
+typedef int fz_v8i __attribute__((ext_vector_type(8)));
+typedef float fz_v16f __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ fz_v16f fz_mfma(const fz_v8i &a, const fz_v8i &b, const fz_v16f &c) {       // both operands e2m1, scales 2^0
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 0, 0, 0);
+}
+
+// XCD-aware block -> (window, part), as the pair kernels deal their blocks (pg_pair_mfma.hip)
+__device__ __forceinline__ bool fuse_win_decode(int per_win, int n_win, int &win, int &rem) {
+    const int xcd = blockIdx.x & 7;
+    const int v = blockIdx.x >> 3;
+    const int full = n_win >> 3;
+    if (v < full * per_win) {
+        win = (v / per_win) * 8 + xcd;
+        rem = v % per_win;
+        return true;
+    }
+    const int total = (n_win & 7) * per_win, q = (total + 7) >> 3;
+    const int vt = v - full * per_win, lin = xcd * q + vt;
+    if (vt >= q || lin >= total) return false;
+    win = full * 8 + lin / per_win;
+    rem = lin % per_win;
+    return true;
+}
+
+template <int DIP>
+__device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
+                                            const int64_t *__restrict__ win_hi, const int64_t *__restrict__ goff,
+                                            uint32_t *__restrict__ XV, int NP, int32_t *__restrict__ nw,
+                                            int32_t *__restrict__ mismatch, int capg, const PgFuseArgs &fa) {
+    constexpr int VN = DIP ? 4 : 8;                      // units per lane
+    extern __shared__ uint4 fz_lds[];                    // frag[NB][8][32 T] | stage_x[8 waves][PACK_FUSE_XC * 4][64 lanes] | counters
+    int b, kp;
+    if (!fuse_win_decode(fa.kparts, fa.n_win, b, kp)) return;          // block-uniform
+    const int UW = 32 * fa.T;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint4 *const frag = fz_lds;
+    uint4 *const stage_x = fz_lds + PACK_FUSE_NB * 8 * UW + wave * (PACK_FUSE_XC * 4 * 64);
+    // ready[k]: waves that have written their cells of the iterations k, k + NB, ...; done[k]: waves that have read them
+    int *const ready = reinterpret_cast<int *>(fz_lds + PACK_FUSE_NB * 8 * UW + 8 * (PACK_FUSE_XC * 4 * 64)), *const done = ready + PACK_FUSE_NB;
+    const int64_t lo = win_lo[b], hi = win_hi[b];
+    const int W = (int)((hi - lo + 31) >> 5);
+    const int w_begin = (int)((long long)W * kp / fa.kparts), w_end = (int)((long long)W * (kp + 1) / fa.kparts);
+    const int nit = (w_end - w_begin + 7) >> 3;
+    const int h0 = 8 * lane;                 // first slot of this lane; its row dword starts at byte 4 * lane
+    const bool has_data = h0 < 2 * RS;
+    const int u0 = VN * lane;
+    int cnt = 0, nxs = 0;
+    uint32_t MA = 0u, ME = 0u;
+    uint32_t cur[8], xo[8], vo[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cur[k] = xo[k] = vo[k] = 0u;
+    uint32_t bad = 0u;
+    uint32_t *xv_base = XV + (size_t)goff[b] * capg * PG_XV_PLANES * (size_t)NP;
+    const int capw = (int)(goff[b + 1] - goff[b]) * capg;          // words reserved for this window
+    auto flush_x = [&]() {                   // the staged words leave together, into consecutive slots of the window's area
+        if (!nxs) return;
+        int s0 = 0;
+        if (lane == 0) s0 = atomicAdd(&nw[b], nxs);
+        const int slot0 = __builtin_amdgcn_readfirstlane(s0);
+        for (int k = 0; k < nxs; ++k) {
+            if (slot0 + k >= capw) {         // more virtual sites than reserved: the host redoes the batch with the worst-case reservation
+                if (lane == 0) atomicOr(mismatch, 2);
+            } else if (has_data) {
+                uint4 *o = reinterpret_cast<uint4 *>(xv_base + (size_t)(slot0 + k) * PG_XV_PLANES * (size_t)NP + 2 * h0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = stage_x[(4 * k + i) * 64 + lane];
+            }
+        }
+        nxs = 0;
+    };
+    auto store_word = [&]() {
+        if (has_data) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) stage_x[(4 * nxs + i) * 64 + lane] = make_uint4(xo[2 * i], vo[2 * i], xo[2 * i + 1], vo[2 * i + 1]);
+        }
+        if (++nxs == PACK_FUSE_XC) flush_x();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) xo[k] = vo[k] = 0u;
+    };
+    auto finish_dword = [&](int qd) {        // 8 entries (nibbles of cur[k]) -> bits 4j+qd of the two planes
+        const uint32_t nME = ~ME;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t cx = (((cur[k] & MA) + 0x77777777u) >> 3) & 0x11111111u;
+            const uint32_t cv = (((cur[k] & nME) + 0x77777777u) >> 3) & 0x11111111u;
+            xo[k] |= cx << qd;
+            vo[k] |= cv << qd;
+            cur[k] = 0u;
+        }
+        MA = 0u;
+        ME = 0u;
+    };
+    auto append = [&](const uint32_t (&Rq)[8], int j, uint32_t A, uint32_t E) {       // j, A, E uniform
+        const int sh = 4 * (cnt & 7);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) cur[k] |= __builtin_amdgcn_ubfe(Rq[k], 4 * j, 4) << sh;
+        MA |= A << sh;
+        ME |= E << sh;
+        ++cnt;
+        if ((cnt & 7) == 0) {
+            finish_dword((cnt >> 3) - 1);
+            if (cnt == 32) {
+                store_word();
+                cnt = 0;
+            }
+        }
+    };
+    // the rows of one word: a descriptor of its own (a part may be longer than 32-bit offsets reach); a word past the part reads as zero
+    auto word_rsrc = [&](int w) -> __amdgpu_buffer_rsrc_t {
+        const int64_t row = lo + 32ll * w;
+        const int n = w < w_end ? (int)((hi - row) < 32 ? (hi - row) : 32) : 0;
+        return group_rsrc(gt, RS, n ? row : lo, n);
+    };
+    // this wave's products: cells of tile row a[p] and tile column b[p & 1] of the word with this lane half's parity
+    const int r = lane & 31, kb = lane >> 5;
+    int ia[4], ib[2];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) ia[p] = kb * UW + 32 * (int)fa.a[wave][p] + r;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) ib[p] = kb * UW + 32 * (int)fa.b[wave][p] + r;
+    fz_v16f acc[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[p][e] = 0.0f;
+    auto products_step = [&](const uint4 *fb, int s) {   // K step s of one iteration's cells
+        {
+            fz_v8i fa_[4], fb_[2];               // fp4 operands are the first four registers; the others are not read
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const uint4 x = fb[2 * s * UW + ia[p]];
+                fa_[p][0] = (int)x.x; fa_[p][1] = (int)x.y; fa_[p][2] = (int)x.z; fa_[p][3] = (int)x.w;
+            }
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const uint4 x = fb[2 * s * UW + ib[p]];
+                fb_[p][0] = (int)x.x; fb_[p][1] = (int)x.y; fb_[p][2] = (int)x.z; fb_[p][3] = (int)x.w;
+            }
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                acc[p] = fz_mfma(fa_[p], fb_[p & 1], acc[p]);
+        }
+    };
+    // (iteration 0 "reads" the cells of slot NB - 1: zeros, counted as done before they were ever written)
+    if (threadIdx.x < 2 * PACK_FUSE_NB) ready[threadIdx.x] = threadIdx.x == 2 * PACK_FUSE_NB - 1 ? -8 : 0;
+    for (int i = threadIdx.x; i < 8 * UW; i += 512) frag[(PACK_FUSE_NB - 1) * 8 * UW + i] = make_uint4(0u, 0u, 0u, 0u);
+    // The waves meet through these counters, not through barriers: a barrier per iteration keeps all eight waiting for the slowest
+    // row loads of every word (measured: + 0.8 ms per north-star pass).  A poll that never succeeds ends after PACK_FUSE_SPINS
+    // tries and raises PG_FLAG_FUSE_STALL: the call fails instead of the kernel hanging.
+    bool stalled = false;
+    auto wait_ge = [&](int *ctr, int target) {
+        for (int spins = 0; __builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < target;) {
+            __builtin_amdgcn_s_sleep(1);
+            if (++spins > PACK_FUSE_SPINS) { stalled = true; break; }
+        }
+    };
+    auto arrive = [&](int *ctr) {            // after this wave's LDS reads / writes so far
+        if (lane == 0) __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    uint32_t dn[32];
+#pragma unroll
+    for (int s = 0; s < 32; ++s) dn[s] = 0u;
+    const RowOff ro = make_row_off(RS);
+    // (a lane past the row reads past every descriptor: zeros, no branch around the loads)
+    const int lane_off = has_data ? 4 * lane : 0x40000000;
+    word_load(word_rsrc(w_begin + wave), lane_off, RS, 0, ro, dn);
+    __syncthreads();
+    int slot = 0, round8 = 0, pslot = PACK_FUSE_NB - 1, pround8 = -8;        // it % NB, 8 (it / NB); the same of it - 1
+    for (int it = 0; it < nit; ++it) {
+        const int w = w_begin + 8 * it + wave;
+        uint32_t pa[4] = {0u, 0u, 0u, 0u};
+        uint32_t R[4][8];
+        const bool live = w < w_end;            // wave-uniform
+        uint32_t d[32];
+#pragma unroll
+        for (int s = 0; s < 32; ++s) d[s] = dn[s];
+        word_load(word_rsrc(w + 8), lane_off, RS, 0, ro, dn);
+        // K step q of the cells of the iteration before, then the transposes of sites 8q .. 8q+7: one basic block, so that the
+        // matrix pipe works under this wave's own vector instructions (a word past the part and a lane past the row transpose zeros)
+        // The products over the cells of the iteration before are issued one at a time between the pieces of this word's transposes
+        // (the order is pinned: left to itself the scheduler puts the sixteen products in a row, and the wave stands still while the
+        // matrix pipe works through them: + 0.5 ms per north-star pass).  Iteration 0 multiplies the zeroed cells of slot NB - 1.
+        wait_ge(&ready[pslot], pround8 + 8);
+        const uint4 *fb = frag + pslot * 8 * UW;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            fz_v8i fa_[4], fb_[2];               // fp4 operands are the first four registers; the others are not read
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const uint4 x = fb[2 * q * UW + ia[p]];
+                fa_[p][0] = (int)x.x; fa_[p][1] = (int)x.y; fa_[p][2] = (int)x.z; fa_[p][3] = (int)x.w;
+            }
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const uint4 x = fb[2 * q * UW + ib[p]];
+                fb_[p][0] = (int)x.x; fb_[p][1] = (int)x.y; fb_[p][2] = (int)x.z; fb_[p][3] = (int)x.w;
+            }
+            const uint32_t *e = d + 8 * q;
+            uint32_t re[4], rq[4];
+            __builtin_amdgcn_sched_barrier(0);
+            btrans4(bfi_f0(e[1] << 4, e[0]), bfi_f0(e[3] << 4, e[2]), bfi_f0(e[5] << 4, e[4]), bfi_f0(e[7] << 4, e[6]), re);
+            asm volatile("" : "+v"(re[0]), "+v"(re[1]), "+v"(re[2]), "+v"(re[3]));          // (computed here, not where it is first used)
+            __builtin_amdgcn_sched_barrier(0);
+            acc[0] = fz_mfma(fa_[0], fb_[0], acc[0]);
+            __builtin_amdgcn_sched_barrier(0);
+            btrans4(bfi_f0(e[1], e[0] >> 4), bfi_f0(e[3], e[2] >> 4), bfi_f0(e[5], e[4] >> 4), bfi_f0(e[7], e[6] >> 4), rq);
+            asm volatile("" : "+v"(rq[0]), "+v"(rq[1]), "+v"(rq[2]), "+v"(rq[3]));
+            __builtin_amdgcn_sched_barrier(0);
+            acc[1] = fz_mfma(fa_[1], fb_[1], acc[1]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                R[q][2 * k] = re[k];
+                R[q][2 * k + 1] = rq[k];
+            }
+            const uint32_t o = (re[0] | re[1] | re[2] | re[3]) | (rq[0] | rq[1] | rq[2] | rq[3]);      // 8 sites x presence nibble
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const uint32_t piece = (a >= q ? (o >> (a - q)) : (o << (q - a))) & (0x11111111u << q);
+                pa[a] = q ? (pa[a] | piece) : piece;
+            }
+            asm volatile("" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]));
+            __builtin_amdgcn_sched_barrier(0);
+            acc[2] = fz_mfma(fa_[2], fb_[0], acc[2]);
+            acc[3] = fz_mfma(fa_[3], fb_[1], acc[3]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        arrive(&done[pslot]);
+        wait_ge(&done[slot], round8);            // (the cells of iteration it - NB have been read by every wave)
+        {
+            // called = nibble != 0 = bit 3 of (nibble + 7): eight sites of a slot as nibbles 0 / 1, one dword of its fragment.
+            // (DIP: unit = individual 4 lane + k = slots h0 + 2k, h0 + 2k + 1, whose called bits agree unless `bad`)
+            uint4 *cell = frag + (slot * 8 + wave) * UW + u0;
+#pragma unroll
+            for (int k = 0; k < VN; ++k) {
+                const int hk = DIP ? 2 * k : k;
+                uint32_t c[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint32_t t = R[q][hk] + 0x77777777u;
+                    if (DIP) bad |= t ^ (R[q][hk + 1] + 0x77777777u);
+                    c[q] = (t >> 3) & 0x11111111u;
+                }
+                if (u0 + k < UW) cell[k] = make_uint4(c[0], c[1], c[2], c[3]);
+            }
+        }
+        arrive(&ready[slot]);
+        if (live) {
+            uint32_t pr[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) pr[a] = pa[a];
+            wave_or4(pr);
+            const uint32_t m0 = poly_mask(pr);
+            if (m0) {
+                const int lb = lane & 31;
+                const uint32_t Pl = __builtin_amdgcn_ubfe(pr[0], lb, 1) | (__builtin_amdgcn_ubfe(pr[1], lb, 1) << 1) |
+                                    (__builtin_amdgcn_ubfe(pr[2], lb, 1) << 2) | (__builtin_amdgcn_ubfe(pr[3], lb, 1) << 3);
+                const uint32_t A0l = Pl & (0u - Pl);
+                // virtual site 0 of every polymorphic site: tests the lowest allele present, excludes nothing
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    uint32_t mq = m0 & (0x11111111u << q);
+                    while (mq) {
+                        const int bit = __builtin_ctz(mq);
+                        mq &= mq - 1u;
+                        append(R[q], bit >> 2, (uint32_t)__builtin_amdgcn_readlane((int)A0l, bit), 0u);
+                    }
+                }
+                // rare: the second / third virtual site of the sites with three / four alleles
+                const uint32_t m3 = tri_mask(pr);
+                if (m3) {
+#pragma unroll 1
+                    for (int pass = 1; pass < 3; ++pass) {
+                        uint32_t m = pass == 1 ? m3 : quad_mask(pr);
+                        while (m) {
+                            const int bit = __builtin_ctz(m);
+                            m &= m - 1u;
+                            const uint32_t P = (uint32_t)__builtin_amdgcn_readlane((int)Pl, bit);
+                            const uint32_t A0 = P & (0u - P), P1 = P ^ A0, A1 = P1 & (0u - P1), P2 = P1 ^ A1, A2 = P2 & (0u - P2);
+                            const uint32_t A = pass == 1 ? A1 : A2;
+                            const int q = bit & 3;                        // uniform
+                            if (q == 0) append(R[0], bit >> 2, A, (A - 1u) & P);
+                            else if (q == 1) append(R[1], bit >> 2, A, (A - 1u) & P);
+                            else if (q == 2) append(R[2], bit >> 2, A, (A - 1u) & P);
+                            else append(R[3], bit >> 2, A, (A - 1u) & P);
+                        }
+                    }
+                }
+            }
+        }
+        pslot = slot;
+        pround8 = round8;
+        if (++slot == PACK_FUSE_NB) { slot = 0; round8 += 8; }
+    }
+    wait_ge(&ready[pslot], pround8 + 8);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) products_step(frag + pslot * 8 * UW, q);
+    if (stalled && lane == 0) atomicOr(mismatch, PG_FLAG_FUSE_STALL);
+    if (cnt & 7) finish_dword(cnt >> 3);
+    if (cnt) store_word();
+    flush_x();
+    if (DIP && (bad & 0x88888888u)) atomicOr(mismatch, 1);
+    // accumulator tiles (count / 4) -> upper triangle of the window's matrix: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    const int n = fa.n_units, atomic = fa.kparts > 1;
+    int32_t *Cw = fa.Cmat + (size_t)b * n * n;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        if (!((fa.mask[wave] >> p) & 1)) continue;
+        const int I = fa.a[wave][p], J = fa.b[wave][p & 1];
+        const int col = 32 * J + (lane & 31);
+        if (col >= n) continue;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int row = 32 * I + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+            if (row >= n || row > col || (row == col && !fa.diag)) continue;
+            const int32_t v = (int32_t)(acc[p][reg] * 4.0f);
+            int32_t *dst = &Cw[(size_t)row * n + col];
+            if (atomic) { if (v) atomicAdd(dst, v); }
+            else *dst = v;
+        }
+    }
+}
+
 // BURST: the plane stores of a thread wait in LDS cells of its own (no barrier) and leave together -- the called plane every
 // `fq` word quadruples, the virtual-site words as many at a time as the rest of the cells hold, with ONE reservation of consecutive slots -- because a store
 // burst costs the HBM fewer read <-> write turn-arounds than the same bytes trickling out between the row loads
 // (tools/ubench/pack_rw.hip: - 4.5 % on the kernel's bare traffic; the kernel's time does not depend on the waves per CU down to
 // three blocks, so the 48 KB of LDS cost nothing).  Blocks of one or two waves only (LDS).
 constexpr int PACK_CELLS = 24;                       // uint4 LDS cells per thread (24 KB per one-wave block: six blocks per CU)
-template <int TPB, int DIP, int BURST>
+// FUSE = 1 (TPB = 512, BURST = 0): the fused form above, one block per window part; fa is read by that form only
+template <int TPB, int DIP, int BURST, int FUSE>
 __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
                                                const int64_t *__restrict__ win_hi, const int64_t *__restrict__ goff,
                                                const int64_t *__restrict__ vgoff, uint32_t *__restrict__ Vp, int NPv,
                                                uint32_t *__restrict__ XV, int NP, int32_t *__restrict__ nw,
-                                               int32_t *__restrict__ mismatch, int capg, int grp, int fq, int perm) {
+                                               int32_t *__restrict__ mismatch, int capg, int grp, int fq, int perm, PgFuseArgs fa) {
+    if constexpr (FUSE) {
+        pack3_fused<DIP>(gt, RS, win_lo, win_hi, goff, XV, NP, nw, mismatch, capg, fa);
+        return;
+    }
     constexpr int NWAVE = TPB / 64;
     constexpr int VN = DIP ? 4 : 8;                      // uint4 of called plane per thread and word quadruple
     const int FQ = fq, xc = (PACK_CELLS - fq * VN) / 4;  // quadruples per burst of the called plane; virtual-site words per burst
@@ -751,7 +1108,7 @@ static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *g
     const bool force2 = getenv("PG_PACK2") != nullptr;
     if (threads <= 1024 && !force2) {
         const int lanes = (threads + 1) / 2;
-#define PG_PACK3B(T, B) hipLaunchKernelGGL((k_pack3<T, DIP, B>), grid, dim3(T), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, capg, grp, fq, perm)
+#define PG_PACK3B(T, B) hipLaunchKernelGGL((k_pack3<T, DIP, B, 0>), grid, dim3(T), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, capg, grp, fq, perm, PgFuseArgs())
 #define PG_PACK3(T) PG_PACK3B(T, 0)
         // quadruples of the called plane per burst (the rest of the 24 LDS cells per thread holds virtual-site words: two)
         const int fq = DIP ? 4 : 2;
@@ -788,6 +1145,93 @@ static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *g
         hipLaunchKernelGGL(k_word_scan, dim3(grid.y), dim3(256), 0, st, win_lo, win_hi, goff, pres, nw, grp);
         hipLaunchKernelGGL((k_pack2<256, DIP, 1>), grid, dim3(256), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
     }
+}
+
+// ---- the fused form: domain, tile tasks, launch ----
+// What it takes: called counts that k_pairC_big would form (up to 7 tiles of 32 units, matrix-core pairs) and rows that one wave
+// spans (up to 512 slots).  Where it pays: what it saves -- the plane's traffic and k_pairC_big's time -- grows with the units
+// (squared, for the products), what it costs -- eight waves coupled in one block that fills a CU -- does not, and a call of few
+// windows has to be cut into parts with atomics.  Measured per pass (profiles/r08): 200 units x 2000 windows of 50 kb 5.5 against
+// 6.15 ms; 100 units x 2000 windows of 5 kb 0.755 against 0.70; 100 units x 200 windows of 50 kb, six parts each, 0.77 against
+// 0.66.  So by itself the library takes it from 1024 windows a call and more than 128 units (five tiles) on; the unit bound lies
+// between the two measured unit counts and is not itself measured.  PG_PACK_FUSE=1 takes it anywhere in its domain (tests: parts
+// and atomics, small unit counts), PG_PACK_FUSE=0 keeps the two kernels (A/B runs, tests), and so does every switch that tunes
+// or selects them.
+bool pg_pack_fuse_fits(int NP, int NPv, int n_units, int n_win) {
+    const char *f = getenv("PG_PACK_FUSE");
+    if (f ? atoi(f) == 0 : (n_win < 1024 || n_units <= 128)) return false;
+    for (const char *e : {"PG_PAIR_VALU", "PG_PACK2", "PG_PACK_BURST", "PG_GROUP_WORDS", "PG_PACK_BLOCKS_PER_CU", "PG_OVERLAP", "PG_PACK_PERM"})
+        if (getenv(e)) return false;
+    return NP <= 512 && n_units >= 1 && pg_pair_big_fits(NPv, n_units);
+}
+
+// Tiles of the upper triangle of T x T dealt to the 8 waves, four products a[p] x b[p & 1] each: 2 x 2 blocks of tile rows
+// (2i, 2i+1) x tile columns (2j, 2j+1), j >= i -- six of them up to T = 6 --; at T = 7 the last tile column goes to two waves of its
+// own, rows 0 .. 3 and 4 .. 6 (28 tiles, 4 + 3 of them there).  Products outside the triangle run on cell 0 and are not stored.
+static void pg_fuse_tasks(int T, PgFuseArgs &fa) {
+    memset(fa.a, 0, sizeof fa.a);
+    memset(fa.b, 0, sizeof fa.b);
+    memset(fa.mask, 0, sizeof fa.mask);
+    const int Tb = T == 7 ? 6 : T;
+    int wv = 0;
+    for (int i = 0; i < Tb; i += 2)
+        for (int j = i; j < Tb; j += 2, ++wv)
+            for (int p = 0; p < 4; ++p) {
+                const int I = i + (p >> 1), J = j + (p & 1);
+                if (I < Tb && J < Tb && I <= J) {
+                    fa.a[wv][p] = (signed char)I;
+                    fa.b[wv][p & 1] = (signed char)J;
+                    fa.mask[wv] |= (unsigned char)(1u << p);
+                }
+            }
+    if (T == 7)
+        for (int i = 0; i < 7; i += 4, ++wv) {
+            fa.b[wv][0] = fa.b[wv][1] = 6;
+            for (int p = 0; p < 4 && i + p < 7; ++p) {
+                fa.a[wv][p] = (signed char)(i + p);
+                fa.mask[wv] |= (unsigned char)(1u << p);
+            }
+        }
+}
+
+// nw[0 .. n_win): zeroed per-window word counters, as for pg_launch_pack2.  max_words / avg_words: words (32 sites) of the longest /
+// average window of the batch.
+int pg_launch_pack_fused(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi, const int64_t *goff,
+                         int n_win, int64_t max_words, int64_t avg_words, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch,
+                         int capg, int n_units, int32_t *Cmat) {
+    if (n_win <= 0) return 0;
+    PgFuseArgs fa;
+    fa.n_win = n_win;
+    fa.n_units = n_units;
+    fa.T = (n_units + 31) / 32;
+    fa.diag = dip ? 1 : 0;
+    fa.Cmat = Cmat;
+    pg_fuse_tasks(fa.T, fa);
+    // one block fills a CU (8 waves of up to 256 registers): a batch of few windows is cut into parts until the blocks go round
+    // the 256 CUs about four times, as long as a part keeps 64 words (8 iterations); an f32 accumulator holds count / 4 exactly
+    // while count < 2^24: parts below 2^23 sites
+    int64_t kparts = n_win >= 1024 ? 1 : (1024 + n_win - 1) / n_win;
+    kparts = std::min<int64_t>(kparts, std::max<int64_t>(1, avg_words / 64));
+    kparts = std::max<int64_t>(kparts, (max_words * 32 + (1 << 23) - 1) >> 23);
+    fa.kparts = (int)kparts;
+    if (kparts > 1) (void)hipMemsetAsync(Cmat, 0, (size_t)n_win * n_units * n_units * 4, st);
+    const size_t lds = (size_t)(PACK_FUSE_NB * 8 * 32 * fa.T + 8 * PACK_FUSE_XC * 4 * 64 + 2) * sizeof(uint4);
+    const int64_t blocks = (int64_t)((n_win + 7) / 8) * kparts * 8;
+#define PG_PACK3F(D)                                                                                                              \
+    do {                                                                                                                          \
+        static bool ready = false;                       /* more than 64 KB of dynamic LDS: asked for once per form */            \
+        if (!ready) {                                                                                                             \
+            if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pack3<512, D, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                    (PACK_FUSE_NB * 8 * 32 * 7 + 8 * PACK_FUSE_XC * 4 * 64 + 2) * (int)sizeof(uint4)) != hipSuccess) return 1; \
+            ready = true;                                                                                                         \
+        }                                                                                                                         \
+        hipLaunchKernelGGL((k_pack3<512, D, 0, 1>), dim3((unsigned)blocks), dim3(512), lds, st, gt, RS, win_lo, win_hi, goff,         \
+                           (const int64_t *)nullptr, (uint32_t *)nullptr, 0, XV, NP, nw, mismatch, capg, 0, 0, 1, fa);           \
+    } while (0)
+    if (dip) PG_PACK3F(1);
+    else PG_PACK3F(0);
+#undef PG_PACK3F
+    return 0;
 }
 
 // more slots than one k_pack3 block takes (or k_pack2 forced beyond one of ITS blocks): the presence pre-pass runs
