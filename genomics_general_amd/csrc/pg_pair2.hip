@@ -198,6 +198,73 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t group_rsrc(const int8_t *gt, i
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t *>(gt + first_row * (int64_t)RS), 0, nrows * RS, 0x00020000);
 }
 
+// The thread that speaks for NWAVE waves that reserve XV words together: lane 0 of a wave of its own, thread 0 of a block
+template <int NWAVE>
+__device__ __forceinline__ bool xv_leader() { return (NWAVE == 1 ? threadIdx.x & 63 : threadIdx.x) == 0; }
+
+// The XV area of one window as one thread of a pack kernel sees it (the thread owns slots h0 .. and the words from 2 * h0 of
+// every XV word), and the one rule for a word that the reservation does not hold.
+struct XvWin {
+    uint32_t *xv_base;                       // word 0 of the window
+    int NP, h0, capw;                        // capw: words reserved for this window
+    int32_t *nwb, *mismatch;                 // the window's word counter (nw[b]); the batch's flags
+    bool has_data;                           // the thread has slots below 2 * RS
+
+    // does the thread store its piece of word `slot` (reserved by NWAVE waves together, uniform over them)?
+    template <int NWAVE>
+    __device__ __forceinline__ bool holds(int slot) const {
+        if (slot >= capw) {                  // more virtual sites than reserved: the host redoes the batch with the worst-case reservation
+            if (xv_leader<NWAVE>()) atomicOr(mismatch, 2);
+            return false;
+        }
+        return has_data;
+    }
+    __device__ __forceinline__ uint32_t *word(int slot) const { return xv_base + (size_t)slot * PG_XV_PLANES * (size_t)NP + 2 * h0; }
+};
+
+// window b's area: goff[b] * capg words in, (goff[b + 1] - goff[b]) * capg words long
+__device__ __forceinline__ XvWin make_xv_win(uint32_t *XV, const int64_t *goff, int b, int capg, int NP, int h0, int32_t *nw,
+                                             int32_t *mismatch, bool has_data) {
+    return {XV + (size_t)goff[b] * capg * PG_XV_PLANES * (size_t)NP, NP, h0, (int)(goff[b + 1] - goff[b]) * capg, &nw[b], mismatch, has_data};
+}
+
+// n consecutive words of the window's XV area, reserved by the NWAVE waves of a block together (block-uniform result)
+template <int NWAVE>
+__device__ __forceinline__ int xv_reserve(int32_t *nwb, int n, int *sh_slot) {
+    if (NWAVE == 1) {
+        int s0 = 0;
+        if (xv_leader<1>()) s0 = atomicAdd(nwb, n);
+        return __builtin_amdgcn_readfirstlane(s0);
+    }
+    if (xv_leader<NWAVE>()) *sh_slot = atomicAdd(nwb, n);
+    __syncthreads();
+    const int slot = __builtin_amdgcn_readfirstlane(*sh_slot);
+    __syncthreads();
+    return slot;
+}
+
+// OR of four values over the block: wave_or4, then the waves' totals meet in sh_pres[parity] (one barrier per call; the two
+// parities keep a fast wave's next totals apart from the ones a slow wave still reads)
+template <int NWAVE>
+__device__ __forceinline__ void block_or4(uint32_t pr[4], uint32_t (*sh_pres)[NWAVE][4], int &parity, int lane) {
+    wave_or4(pr);
+    if (NWAVE > 1) {
+        if (lane == 0) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) sh_pres[parity][threadIdx.x >> 6][a] = pr[a];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            uint32_t x = 0u;
+#pragma unroll
+            for (int wv = 0; wv < NWAVE; ++wv) x |= sh_pres[parity][wv][a];
+            pr[a] = __builtin_amdgcn_readfirstlane(x);
+        }
+        parity ^= 1;
+    }
+}
+
 // More than 1024 haplotype slots do not fit one block: k_presence (phase A only, grid.z = blocks of 1024 slots) first ORs the
 // presence nibbles of all slot blocks into pres[word][4]; k_pack2<.,.,PRES=1> then reads them.
 __global__ __launch_bounds__(256) void k_presence(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
@@ -300,28 +367,13 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
     uint32_t vlist = (uint32_t)nrows;        // lane i = list entry i; "nrows" is one row past the descriptor: reads as zero
     int cnt = 0, nflush = 0, parity = 0;
     uint32_t bad = 0u;
-    uint32_t *xv_base = XV + (size_t)goff[b] * capg * PG_XV_PLANES * (size_t)NP;
-    const int capw = (int)(goff[b + 1] - goff[b]) * capg;          // words reserved for this window
+    const XvWin xw = make_xv_win(XV, goff, b, capg, NP, h0, nw, mismatch, has_data);
     const uint32_t *pres_g = pres + (size_t)(goff[b] + g) * grp * 4u;       // PRES only
     const int64_t vg_base = vgoff[b] + (int64_t)(w_begin >> 2);
     // PRES: the group's words start at gbase (k_word_scan); otherwise every flush takes the window's next free word
     const int gbase = PRES ? nw[n_win + goff[b] + g] : 0;
     auto flush = [&]() {                     // the first 32 list entries become one dense word of XV
-        int slot;
-        if (PRES) {
-            slot = gbase + nflush;
-        } else {
-            if (NWAVE == 1) {
-                int s0 = 0;
-                if (lane == 0) s0 = atomicAdd(&nw[b], 1);
-                slot = __builtin_amdgcn_readfirstlane(s0);
-            } else {
-                if (threadIdx.x == 0) sh_slot = atomicAdd(&nw[b], 1);
-                __syncthreads();
-                slot = __builtin_amdgcn_readfirstlane(sh_slot);
-                __syncthreads();
-            }
-        }
+        const int slot = PRES ? gbase + nflush : xv_reserve<NWAVE>(xw.nwb, 1, &sh_slot);
         // which allele each of the 32 entries tests (A) and which alleles it excludes (E), from the presence nibble of its site
         uint32_t A = 0u, E = 0u;
         {
@@ -344,12 +396,10 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
                                 (uint32_t)__builtin_amdgcn_ballot_w64(A == 4u)};
         const uint32_t SE[2] = {(uint32_t)__builtin_amdgcn_ballot_w64((E & 1u) != 0u),
                                 (uint32_t)__builtin_amdgcn_ballot_w64((E & 2u) != 0u)};
-        if (slot >= capw) {                  // more virtual sites than reserved: the host redoes the batch with the worst-case reservation
-            if (threadIdx.x == 0) atomicOr(mismatch, 2);
-        } else if (has_data) {
+        if (xw.holds<NWAVE>(slot)) {
             uint32_t x[PG_XV_PLANES][4];
             poly_word(rsrc, h0, RS, vlist, SA, SE, x);
-            uint32_t *o = xv_base + (size_t)slot * PG_XV_PLANES * (size_t)NP + 2 * h0;
+            uint32_t *o = xw.word(slot);
             store16(o, x[0][0], x[1][0], x[0][1], x[1][1]);
             store16(o + 4, x[0][2], x[1][2], x[0][3], x[1][3]);
         }
@@ -387,22 +437,7 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
                 } else {
 #pragma unroll
                     for (int a = 0; a < 4; ++a) pr[a] = pa[a];
-                    wave_or4(pr);
-                }
-                if (!PRES && NWAVE > 1) {
-                    if (lane == 0) {
-#pragma unroll
-                        for (int a = 0; a < 4; ++a) sh_pres[parity][threadIdx.x >> 6][a] = pr[a];
-                    }
-                    __syncthreads();
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) {
-                        uint32_t x = 0u;
-#pragma unroll
-                        for (int wv = 0; wv < NWAVE; ++wv) x |= sh_pres[parity][wv][a];
-                        pr[a] = __builtin_amdgcn_readfirstlane(x);
-                    }
-                    parity ^= 1;
+                    block_or4<NWAVE>(pr, sh_pres, parity, lane);
                 }
                 if (!PRES && threadIdx.x == 0) sh_gp[PRES ? 0 : w - w_begin] = make_uint4(pr[0], pr[1], pr[2], pr[3]);
                 const int row_w = (w - w_begin) * 32;
@@ -466,30 +501,188 @@ __global__ __launch_bounds__(TPB) void k_pack2(const int8_t *__restrict__ gt, in
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t bfi_f0(uint32_t hi, uint32_t lo) { return (hi & 0xF0F0F0F0u) | (lo & 0x0F0F0F0Fu); }
 
+// One q (sites 8q .. 8q+7, row dwords e[0 .. 7]) of a word's transposition, in the three pieces the fused form spreads its products
+// between: the even slots' and the odd slots' half transposes, then R[q] and the presence nibbles from both.
+__device__ __forceinline__ void trans_even(const uint32_t e[8], uint32_t r[4]) {
+    btrans4(bfi_f0(e[1] << 4, e[0]), bfi_f0(e[3] << 4, e[2]), bfi_f0(e[5] << 4, e[4]), bfi_f0(e[7] << 4, e[6]), r);
+}
+__device__ __forceinline__ void trans_odd(const uint32_t e[8], uint32_t r[4]) {
+    btrans4(bfi_f0(e[1], e[0] >> 4), bfi_f0(e[3], e[2] >> 4), bfi_f0(e[5], e[4] >> 4), bfi_f0(e[7], e[6] >> 4), r);
+}
+__device__ __forceinline__ void keep_presence(int q, const uint32_t re[4], const uint32_t ro[4], uint32_t Rq[8], uint32_t pa[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        Rq[2 * k] = re[k];
+        Rq[2 * k + 1] = ro[k];
+    }
+    const uint32_t o = (re[0] | re[1] | re[2] | re[3]) | (ro[0] | ro[1] | ro[2] | ro[3]);      // 8 sites x presence nibble
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const uint32_t piece = (a >= q ? (o >> (a - q)) : (o << (q - a))) & (0x11111111u << q);
+        pa[a] = q ? (pa[a] | piece) : piece;
+    }
+}
+
 __device__ __forceinline__ void word_called_presence_keep(const uint32_t d[32], uint32_t v[8], uint32_t pa[4], uint32_t R[4][8]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const uint32_t *e = d + 8 * q;
         uint32_t re[4], ro[4];
-        btrans4(bfi_f0(e[1] << 4, e[0]), bfi_f0(e[3] << 4, e[2]), bfi_f0(e[5] << 4, e[4]), bfi_f0(e[7] << 4, e[6]), re);
-        btrans4(bfi_f0(e[1], e[0] >> 4), bfi_f0(e[3], e[2] >> 4), bfi_f0(e[5], e[4] >> 4), bfi_f0(e[7], e[6] >> 4), ro);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            R[q][2 * k] = re[k];
-            R[q][2 * k + 1] = ro[k];
-        }
-        const uint32_t o = (re[0] | re[1] | re[2] | re[3]) | (ro[0] | ro[1] | ro[2] | ro[3]);      // 8 sites x presence nibble
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            const uint32_t piece = (a >= q ? (o >> (a - q)) : (o << (q - a))) & (0x11111111u << q);
-            pa[a] = q ? (pa[a] | piece) : piece;
-        }
+        trans_even(d + 8 * q, re);
+        trans_odd(d + 8 * q, ro);
+        keep_presence(q, re, ro, R[q], pa);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             // called = nibble != 0 = bit 3 of (nibble + 7); moved to bit q of the nibble
             const uint32_t t = R[q][k] + 0x77777777u;
             const uint32_t c = (q == 3 ? t : (t >> (3 - q))) & (0x11111111u << q);
             v[k] = q ? (v[k] | c) : c;
+        }
+    }
+}
+
+// Where k_pack3's finished XV words go.  STAGED: they wait in LDS cells of the thread's own (cell[i * stride], no barrier) and
+// leave `burst` at a time, into consecutive slots of the window reserved with ONE atomic -- a store burst costs the HBM fewer
+// read <-> write turn-arounds than the same bytes trickling out between the row loads (tools/ubench/pack_rw.hip: - 4.5 % on the
+// kernel's bare traffic).  Otherwise every word reserves its slot and is stored at once.  NWAVE: the waves that reserve together
+// (1 in the fused form, where each wave of the block packs words of its own).
+template <int NWAVE, bool STAGED>
+struct XvSink {
+    XvWin win;
+    int *sh_slot;                            // xv_reserve's cell (not read at NWAVE = 1: nullptr there)
+    uint4 *cell;                             // STAGED only, as stride, burst and nxs (otherwise whatever the caller has: never read)
+    int stride, burst;
+    int nxs;                                 // staged words (uniform over the reserving threads)
+
+    __device__ __forceinline__ XvSink(const XvWin &w, int *sh_slot_, uint4 *cell_, int stride_, int burst_)
+        : win(w), sh_slot(sh_slot_), cell(cell_), stride(stride_), burst(burst_), nxs(0) {}
+    __device__ __forceinline__ void flush() {
+        if (!nxs) return;
+        const int slot0 = xv_reserve<NWAVE>(win.nwb, nxs, sh_slot);
+        for (int k = 0; k < nxs; ++k)
+            if (win.template holds<NWAVE>(slot0 + k)) {
+                uint4 *o = reinterpret_cast<uint4 *>(win.word(slot0 + k));
+#pragma unroll
+                for (int i = 0; i < 4; ++i) o[i] = cell[(4 * k + i) * stride];
+            }
+        nxs = 0;
+    }
+    // the planes of the thread's eight slots over 32 virtual sites become one dense word of XV (the window's next free word)
+    __device__ __forceinline__ void put(const uint32_t xo[8], const uint32_t vo[8]) {
+        if (STAGED) {
+            if (win.has_data) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) cell[(4 * nxs + i) * stride] = make_uint4(xo[2 * i], vo[2 * i], xo[2 * i + 1], vo[2 * i + 1]);
+            }
+            if (++nxs == burst) flush();
+        } else {
+            const int slot = xv_reserve<NWAVE>(win.nwb, 1, sh_slot);
+            if (win.template holds<NWAVE>(slot)) {
+                uint32_t *o = win.word(slot);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) store16(o + 4 * i, xo[2 * i], vo[2 * i], xo[2 * i + 1], vo[2 * i + 1]);
+            }
+        }
+    }
+};
+
+// a dword of nibbles that are 0 or one-hot -> 1 in every nibble that is not 0 (bit 3 of nibble + 7)
+__device__ __forceinline__ uint32_t nz_nibbles(uint32_t x) { return ((x + 0x77777777u) >> 3) & 0x11111111u; }
+
+// The compaction described over k_pack3, the one copy every route through k_pack3 runs: append() takes one polymorphic site's
+// nibbles of the thread's eight slots (Rq, site j of them) with the allele A the entry tests and the alleles E it excludes, every 8
+// entries become 8 bits of x and v, every 32 one word for the sink.  cnt, MA, ME are uniform.
+// (The arrays come first: as compiled today, with the scalars in front of them three instantiations keep ME in a vector register,
+// one VGPR more.  An observation on this compiler, not a rule.)
+
+template <class Sink>
+struct VsCompactor {
+    uint32_t cur[8], xo[8], vo[8];
+    int cnt;                                 // entries of the pending output word (0..31)
+    uint32_t MA, ME;                         // nibble masks of the pending 8-entry dword
+    Sink &out;
+
+    __device__ __forceinline__ explicit VsCompactor(Sink &s) : cnt(0), MA(0u), ME(0u), out(s) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) cur[k] = xo[k] = vo[k] = 0u;
+    }
+    __device__ __forceinline__ void finish_dword(int qd) {       // 8 entries (nibbles of cur[k]) -> bits 4j+qd of the two planes
+        const uint32_t nME = ~ME;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            xo[k] |= nz_nibbles(cur[k] & MA) << qd;
+            vo[k] |= nz_nibbles(cur[k] & nME) << qd;
+            cur[k] = 0u;
+        }
+        MA = 0u;
+        ME = 0u;
+    }
+    __device__ __forceinline__ void store_word() {
+        out.put(xo, vo);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) xo[k] = vo[k] = 0u;
+    }
+    __device__ __forceinline__ void append(const uint32_t (&Rq)[8], int j, uint32_t A, uint32_t E) {       // j, A, E uniform
+        const int sh = 4 * (cnt & 7);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) cur[k] |= __builtin_amdgcn_ubfe(Rq[k], 4 * j, 4) << sh;
+        MA |= A << sh;
+        ME |= E << sh;
+        ++cnt;
+        if ((cnt & 7) == 0) {
+            finish_dword((cnt >> 3) - 1);
+            if (cnt == 32) {
+                store_word();
+                cnt = 0;
+            }
+        }
+    }
+    __device__ __forceinline__ void finish() {                   // the last, partial word (staged words stay with the sink)
+        if (cnt & 7) finish_dword(cnt >> 3);
+        if (cnt) store_word();
+    }
+};
+
+// The polymorphic sites of one word join the compactor.  pr[a] (uniform): sites at which allele a occurs among all slots; R[q][k]:
+// the word's transposed dwords of the thread's slot k.
+template <class Sink>
+__device__ __forceinline__ void emit_poly_sites(const uint32_t pr[4], const uint32_t (&R)[4][8], VsCompactor<Sink> &vs, int lane) {
+    const uint32_t m0 = poly_mask(pr);
+    if (m0) {
+        // lane l (mod 32) works out the presence nibble of the site at mask bit l and its lowest allele, so that the scalar loops
+        // below fetch them with one v_readlane per entry instead of a dozen scalar bit operations
+        const int lb = lane & 31;
+        const uint32_t Pl = __builtin_amdgcn_ubfe(pr[0], lb, 1) | (__builtin_amdgcn_ubfe(pr[1], lb, 1) << 1) |
+                            (__builtin_amdgcn_ubfe(pr[2], lb, 1) << 2) | (__builtin_amdgcn_ubfe(pr[3], lb, 1) << 3);
+        const uint32_t A0l = Pl & (0u - Pl);
+        // virtual site 0 of every polymorphic site: tests the lowest allele present, excludes nothing
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t mq = m0 & (0x11111111u << q);
+            while (mq) {
+                const int bit = __builtin_ctz(mq);
+                mq &= mq - 1u;
+                vs.append(R[q], bit >> 2, (uint32_t)__builtin_amdgcn_readlane((int)A0l, bit), 0u);
+            }
+        }
+        // rare: the second / third virtual site of the sites with three / four alleles
+        const uint32_t m3 = tri_mask(pr);
+        if (m3) {
+#pragma unroll 1
+            for (int pass = 1; pass < 3; ++pass) {
+                uint32_t m = pass == 1 ? m3 : quad_mask(pr);
+                while (m) {
+                    const int bit = __builtin_ctz(m);
+                    m &= m - 1u;
+                    const uint32_t P = (uint32_t)__builtin_amdgcn_readlane((int)Pl, bit);
+                    const uint32_t A0 = P & (0u - P), P1 = P ^ A0, A1 = P1 & (0u - P1), P2 = P1 ^ A1, A2 = P2 & (0u - P2);
+                    const uint32_t A = pass == 1 ? A1 : A2;
+                    const int q = bit & 3;                        // uniform
+                    if (q == 0) vs.append(R[0], bit >> 2, A, (A - 1u) & P);
+                    else if (q == 1) vs.append(R[1], bit >> 2, A, (A - 1u) & P);
+                    else if (q == 2) vs.append(R[2], bit >> 2, A, (A - 1u) & P);
+                    else vs.append(R[3], bit >> 2, A, (A - 1u) & P);
+                }
+            }
         }
     }
 }
@@ -523,6 +716,21 @@ typedef float fz_v16f __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ fz_v16f fz_mfma(const fz_v8i &a, const fz_v8i &b, const fz_v16f &c) {       // both operands e2m1, scales 2^0
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 0, 0, 0);
+}
+
+// The operands of K step s of one iteration's cells fb: a wave's four tile rows (cells ia[p]) and two tile columns (ib[p]); UW =
+// cells per word.  fp4 operands are the first four registers; the others are not read.
+__device__ __forceinline__ void fuse_frags(const uint4 *fb, int s, int UW, const int ia[4], const int ib[2], fz_v8i fa_[4], fz_v8i fb_[2]) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const uint4 x = fb[2 * s * UW + ia[p]];
+        fa_[p][0] = (int)x.x; fa_[p][1] = (int)x.y; fa_[p][2] = (int)x.z; fa_[p][3] = (int)x.w;
+    }
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const uint4 x = fb[2 * s * UW + ib[p]];
+        fb_[p][0] = (int)x.x; fb_[p][1] = (int)x.y; fb_[p][2] = (int)x.z; fb_[p][3] = (int)x.w;
+    }
 }
 
 // XCD-aware block -> (window, part), as the pair kernels deal their blocks (pg_pair_mfma.hip)
@@ -565,67 +773,12 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
     const int h0 = 8 * lane;                 // first slot of this lane; its row dword starts at byte 4 * lane
     const bool has_data = h0 < 2 * RS;
     const int u0 = VN * lane;
-    int cnt = 0, nxs = 0;
-    uint32_t MA = 0u, ME = 0u;
-    uint32_t cur[8], xo[8], vo[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) cur[k] = xo[k] = vo[k] = 0u;
     uint32_t bad = 0u;
-    uint32_t *xv_base = XV + (size_t)goff[b] * capg * PG_XV_PLANES * (size_t)NP;
-    const int capw = (int)(goff[b + 1] - goff[b]) * capg;          // words reserved for this window
-    auto flush_x = [&]() {                   // the staged words leave together, into consecutive slots of the window's area
-        if (!nxs) return;
-        int s0 = 0;
-        if (lane == 0) s0 = atomicAdd(&nw[b], nxs);
-        const int slot0 = __builtin_amdgcn_readfirstlane(s0);
-        for (int k = 0; k < nxs; ++k) {
-            if (slot0 + k >= capw) {         // more virtual sites than reserved: the host redoes the batch with the worst-case reservation
-                if (lane == 0) atomicOr(mismatch, 2);
-            } else if (has_data) {
-                uint4 *o = reinterpret_cast<uint4 *>(xv_base + (size_t)(slot0 + k) * PG_XV_PLANES * (size_t)NP + 2 * h0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = stage_x[(4 * k + i) * 64 + lane];
-            }
-        }
-        nxs = 0;
-    };
-    auto store_word = [&]() {
-        if (has_data) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) stage_x[(4 * nxs + i) * 64 + lane] = make_uint4(xo[2 * i], vo[2 * i], xo[2 * i + 1], vo[2 * i + 1]);
-        }
-        if (++nxs == PACK_FUSE_XC) flush_x();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) xo[k] = vo[k] = 0u;
-    };
-    auto finish_dword = [&](int qd) {        // 8 entries (nibbles of cur[k]) -> bits 4j+qd of the two planes
-        const uint32_t nME = ~ME;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const uint32_t cx = (((cur[k] & MA) + 0x77777777u) >> 3) & 0x11111111u;
-            const uint32_t cv = (((cur[k] & nME) + 0x77777777u) >> 3) & 0x11111111u;
-            xo[k] |= cx << qd;
-            vo[k] |= cv << qd;
-            cur[k] = 0u;
-        }
-        MA = 0u;
-        ME = 0u;
-    };
-    auto append = [&](const uint32_t (&Rq)[8], int j, uint32_t A, uint32_t E) {       // j, A, E uniform
-        const int sh = 4 * (cnt & 7);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) cur[k] |= __builtin_amdgcn_ubfe(Rq[k], 4 * j, 4) << sh;
-        MA |= A << sh;
-        ME |= E << sh;
-        ++cnt;
-        if ((cnt & 7) == 0) {
-            finish_dword((cnt >> 3) - 1);
-            if (cnt == 32) {
-                store_word();
-                cnt = 0;
-            }
-        }
-    };
+    // this wave's virtual-site words: reserved by the wave alone, in bursts of PACK_FUSE_XC from its own cells
+    typedef XvSink<1, true> Sink;
+    Sink xs(make_xv_win(XV, goff, b, capg, NP, h0, nw, mismatch, has_data), nullptr, /* cell */ stage_x + lane, /* stride */ 64,
+            /* burst */ PACK_FUSE_XC);
+    VsCompactor<Sink> vs(xs);
     // the rows of one word: a descriptor of its own (a part may be longer than 32-bit offsets reach); a word past the part reads as zero
     auto word_rsrc = [&](int w) -> __amdgpu_buffer_rsrc_t {
         const int64_t row = lo + 32ll * w;
@@ -644,24 +797,6 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
     for (int p = 0; p < 4; ++p)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[p][e] = 0.0f;
-    auto products_step = [&](const uint4 *fb, int s) {   // K step s of one iteration's cells
-        {
-            fz_v8i fa_[4], fb_[2];               // fp4 operands are the first four registers; the others are not read
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const uint4 x = fb[2 * s * UW + ia[p]];
-                fa_[p][0] = (int)x.x; fa_[p][1] = (int)x.y; fa_[p][2] = (int)x.z; fa_[p][3] = (int)x.w;
-            }
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const uint4 x = fb[2 * s * UW + ib[p]];
-                fb_[p][0] = (int)x.x; fb_[p][1] = (int)x.y; fb_[p][2] = (int)x.z; fb_[p][3] = (int)x.w;
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-                acc[p] = fz_mfma(fa_[p], fb_[p & 1], acc[p]);
-        }
-    };
     // (iteration 0 "reads" the cells of slot NB - 1: zeros, counted as done before they were ever written)
     if (threadIdx.x < 2 * PACK_FUSE_NB) ready[threadIdx.x] = threadIdx.x == 2 * PACK_FUSE_NB - 1 ? -8 : 0;
     for (int i = threadIdx.x; i < 8 * UW; i += 512) frag[(PACK_FUSE_NB - 1) * 8 * UW + i] = make_uint4(0u, 0u, 0u, 0u);
@@ -696,50 +831,30 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
 #pragma unroll
         for (int s = 0; s < 32; ++s) d[s] = dn[s];
         word_load(word_rsrc(w + 8), lane_off, RS, 0, ro, dn);
-        // K step q of the cells of the iteration before, then the transposes of sites 8q .. 8q+7: one basic block, so that the
-        // matrix pipe works under this wave's own vector instructions (a word past the part and a lane past the row transpose zeros)
-        // The products over the cells of the iteration before are issued one at a time between the pieces of this word's transposes
-        // (the order is pinned: left to itself the scheduler puts the sixteen products in a row, and the wave stands still while the
-        // matrix pipe works through them: + 0.5 ms per north-star pass).  Iteration 0 multiplies the zeroed cells of slot NB - 1.
+        // K step q of the cells of the iteration before, and the transposes of sites 8q .. 8q+7: one basic block, so that the
+        // matrix pipe works under this wave's own vector instructions (a word past the part and a lane past the row transpose zeros).
+        // The products are issued one at a time between the three pieces of word_called_presence_keep's q (the order is pinned
+        // here, not in the pieces: left to itself the scheduler puts the sixteen products in a row, and the wave stands still while
+        // the matrix pipe works through them: + 0.5 ms per north-star pass).  Iteration 0 multiplies the zeroed cells of slot NB - 1.
         wait_ge(&ready[pslot], pround8 + 8);
         const uint4 *fb = frag + pslot * 8 * UW;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            fz_v8i fa_[4], fb_[2];               // fp4 operands are the first four registers; the others are not read
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const uint4 x = fb[2 * q * UW + ia[p]];
-                fa_[p][0] = (int)x.x; fa_[p][1] = (int)x.y; fa_[p][2] = (int)x.z; fa_[p][3] = (int)x.w;
-            }
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const uint4 x = fb[2 * q * UW + ib[p]];
-                fb_[p][0] = (int)x.x; fb_[p][1] = (int)x.y; fb_[p][2] = (int)x.z; fb_[p][3] = (int)x.w;
-            }
-            const uint32_t *e = d + 8 * q;
+            fz_v8i fa_[4], fb_[2];
+            fuse_frags(fb, q, UW, ia, ib, fa_, fb_);
             uint32_t re[4], rq[4];
             __builtin_amdgcn_sched_barrier(0);
-            btrans4(bfi_f0(e[1] << 4, e[0]), bfi_f0(e[3] << 4, e[2]), bfi_f0(e[5] << 4, e[4]), bfi_f0(e[7] << 4, e[6]), re);
+            trans_even(d + 8 * q, re);
             asm volatile("" : "+v"(re[0]), "+v"(re[1]), "+v"(re[2]), "+v"(re[3]));          // (computed here, not where it is first used)
             __builtin_amdgcn_sched_barrier(0);
             acc[0] = fz_mfma(fa_[0], fb_[0], acc[0]);
             __builtin_amdgcn_sched_barrier(0);
-            btrans4(bfi_f0(e[1], e[0] >> 4), bfi_f0(e[3], e[2] >> 4), bfi_f0(e[5], e[4] >> 4), bfi_f0(e[7], e[6] >> 4), rq);
+            trans_odd(d + 8 * q, rq);
             asm volatile("" : "+v"(rq[0]), "+v"(rq[1]), "+v"(rq[2]), "+v"(rq[3]));
             __builtin_amdgcn_sched_barrier(0);
             acc[1] = fz_mfma(fa_[1], fb_[1], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                R[q][2 * k] = re[k];
-                R[q][2 * k + 1] = rq[k];
-            }
-            const uint32_t o = (re[0] | re[1] | re[2] | re[3]) | (rq[0] | rq[1] | rq[2] | rq[3]);      // 8 sites x presence nibble
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const uint32_t piece = (a >= q ? (o >> (a - q)) : (o << (q - a))) & (0x11111111u << q);
-                pa[a] = q ? (pa[a] | piece) : piece;
-            }
+            keep_presence(q, re, rq, R[q], pa);
             asm volatile("" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]));
             __builtin_amdgcn_sched_barrier(0);
             acc[2] = fz_mfma(fa_[2], fb_[0], acc[2]);
@@ -771,43 +886,7 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
 #pragma unroll
             for (int a = 0; a < 4; ++a) pr[a] = pa[a];
             wave_or4(pr);
-            const uint32_t m0 = poly_mask(pr);
-            if (m0) {
-                const int lb = lane & 31;
-                const uint32_t Pl = __builtin_amdgcn_ubfe(pr[0], lb, 1) | (__builtin_amdgcn_ubfe(pr[1], lb, 1) << 1) |
-                                    (__builtin_amdgcn_ubfe(pr[2], lb, 1) << 2) | (__builtin_amdgcn_ubfe(pr[3], lb, 1) << 3);
-                const uint32_t A0l = Pl & (0u - Pl);
-                // virtual site 0 of every polymorphic site: tests the lowest allele present, excludes nothing
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    uint32_t mq = m0 & (0x11111111u << q);
-                    while (mq) {
-                        const int bit = __builtin_ctz(mq);
-                        mq &= mq - 1u;
-                        append(R[q], bit >> 2, (uint32_t)__builtin_amdgcn_readlane((int)A0l, bit), 0u);
-                    }
-                }
-                // rare: the second / third virtual site of the sites with three / four alleles
-                const uint32_t m3 = tri_mask(pr);
-                if (m3) {
-#pragma unroll 1
-                    for (int pass = 1; pass < 3; ++pass) {
-                        uint32_t m = pass == 1 ? m3 : quad_mask(pr);
-                        while (m) {
-                            const int bit = __builtin_ctz(m);
-                            m &= m - 1u;
-                            const uint32_t P = (uint32_t)__builtin_amdgcn_readlane((int)Pl, bit);
-                            const uint32_t A0 = P & (0u - P), P1 = P ^ A0, A1 = P1 & (0u - P1), P2 = P1 ^ A1, A2 = P2 & (0u - P2);
-                            const uint32_t A = pass == 1 ? A1 : A2;
-                            const int q = bit & 3;                        // uniform
-                            if (q == 0) append(R[0], bit >> 2, A, (A - 1u) & P);
-                            else if (q == 1) append(R[1], bit >> 2, A, (A - 1u) & P);
-                            else if (q == 2) append(R[2], bit >> 2, A, (A - 1u) & P);
-                            else append(R[3], bit >> 2, A, (A - 1u) & P);
-                        }
-                    }
-                }
-            }
+            emit_poly_sites(pr, R, vs, lane);
         }
         pslot = slot;
         pround8 = round8;
@@ -815,11 +894,15 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
     }
     wait_ge(&ready[pslot], pround8 + 8);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) products_step(frag + pslot * 8 * UW, q);
+    for (int q = 0; q < 4; ++q) {            // the last iteration's cells: no word left to transpose between the products
+        fz_v8i fa_[4], fb_[2];
+        fuse_frags(frag + pslot * 8 * UW, q, UW, ia, ib, fa_, fb_);
+#pragma unroll
+        for (int p = 0; p < 4; ++p) acc[p] = fz_mfma(fa_[p], fb_[p & 1], acc[p]);
+    }
     if (stalled && lane == 0) atomicOr(mismatch, PG_FLAG_FUSE_STALL);
-    if (cnt & 7) finish_dword(cnt >> 3);
-    if (cnt) store_word();
-    flush_x();
+    vs.finish();
+    xs.flush();
     if (DIP && (bad & 0x88888888u)) atomicOr(mismatch, 1);
     // accumulator tiles (count / 4) -> upper triangle of the window's matrix: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
     const int n = fa.n_units, atomic = fa.kparts > 1;
@@ -843,10 +926,8 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
 }
 
 // BURST: the plane stores of a thread wait in LDS cells of its own (no barrier) and leave together -- the called plane every
-// `fq` word quadruples, the virtual-site words as many at a time as the rest of the cells hold, with ONE reservation of consecutive slots -- because a store
-// burst costs the HBM fewer read <-> write turn-arounds than the same bytes trickling out between the row loads
-// (tools/ubench/pack_rw.hip: - 4.5 % on the kernel's bare traffic; the kernel's time does not depend on the waves per CU down to
-// three blocks, so the 48 KB of LDS cost nothing).  Blocks of one or two waves only (LDS).
+// `fq` word quadruples, the virtual-site words (XvSink) as many at a time as the rest of the cells hold.  The kernel's time does not
+// depend on the waves per CU down to three blocks, so the 48 KB of LDS cost nothing.  Blocks of one or two waves only (LDS).
 constexpr int PACK_CELLS = 24;                       // uint4 LDS cells per thread (24 KB per one-wave block: six blocks per CU)
 // FUSE = 1 (TPB = 512, BURST = 0): the fused form above, one block per window part; fa is read by that form only
 template <int TPB, int DIP, int BURST, int FUSE>
@@ -866,7 +947,7 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
     __shared__ int sh_slot;
     __shared__ uint4 stage[BURST ? PACK_CELLS * TPB : 1];
     uint4 *const stage_v = stage, *const stage_x = stage + FQ * VN * TPB;
-    int nq = 0, nxs = 0, wq_first = 0;                   // staged quadruples / virtual-site words (block-uniform), first staged quadruple
+    int nq = 0, wq_first = 0;                            // staged quadruples (block-uniform), first staged quadruple
     // perm (coprime with the number of windows, 1 = the windows in order): blocks that run at the same time -- consecutive
     // blockIdx.y -- work on windows `perm` apart, i.e. on rows and planes spread over the whole batch instead of one moving
     // stretch of it
@@ -884,63 +965,13 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
     const int64_t first = lo + 32ll * w_begin;
     const int nrows = (int)((hi - first) < 32ll * grp ? (hi - first) : 32ll * grp);
     const __amdgpu_buffer_rsrc_t rsrc = group_rsrc(gt, RS, first, nrows);
-    int cnt = 0, parity = 0;                 // cnt: entries of the pending output word (uniform, 0..31)
-    uint32_t MA = 0u, ME = 0u;               // nibble masks of the pending 8-entry dword (uniform)
-    uint32_t cur[8], xo[8], vo[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) cur[k] = xo[k] = vo[k] = 0u;
+    int parity = 0;
     uint32_t bad = 0u;
-    uint32_t *xv_base = XV + (size_t)goff[b] * capg * PG_XV_PLANES * (size_t)NP;
-    const int capw = (int)(goff[b + 1] - goff[b]) * capg;          // words reserved for this window
     const int64_t vg_base = vgoff[b] + (int64_t)(w_begin >> 2);
-    auto reserve = [&](int n) -> int {       // n consecutive words of the window's XV area (block-uniform result)
-        int slot;
-        if (NWAVE == 1) {
-            int s0 = 0;
-            if (lane == 0) s0 = atomicAdd(&nw[b], n);
-            slot = __builtin_amdgcn_readfirstlane(s0);
-        } else {
-            if (threadIdx.x == 0) sh_slot = atomicAdd(&nw[b], n);
-            __syncthreads();
-            slot = __builtin_amdgcn_readfirstlane(sh_slot);
-            __syncthreads();
-        }
-        return slot;
-    };
-    auto flush_x = [&]() {                   // BURST: the staged words leave together, into consecutive slots
-        if (!nxs) return;
-        const int slot0 = reserve(nxs);
-        for (int k = 0; k < nxs; ++k) {
-            if (slot0 + k >= capw) {         // more virtual sites than reserved: the host redoes the batch with the worst-case reservation
-                if (threadIdx.x == 0) atomicOr(mismatch, 2);
-            } else if (has_data) {
-                uint4 *o = reinterpret_cast<uint4 *>(xv_base + (size_t)(slot0 + k) * PG_XV_PLANES * (size_t)NP + 2 * h0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = stage_x[(4 * k + i) * TPB + t];
-            }
-        }
-        nxs = 0;
-    };
-    auto store_word = [&]() {                // the pending planes become one dense word of XV (the window's next free word)
-        if (BURST) {
-            if (has_data) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) stage_x[(4 * nxs + i) * TPB + t] = make_uint4(xo[2 * i], vo[2 * i], xo[2 * i + 1], vo[2 * i + 1]);
-            }
-            if (++nxs == xc) flush_x();
-        } else {
-            const int slot = reserve(1);
-            if (slot >= capw) {              // more virtual sites than reserved: the host redoes the batch with the worst-case reservation
-                if (threadIdx.x == 0) atomicOr(mismatch, 2);
-            } else if (has_data) {
-                uint32_t *o = xv_base + (size_t)slot * PG_XV_PLANES * (size_t)NP + 2 * h0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) store16(o + 4 * i, xo[2 * i], vo[2 * i], xo[2 * i + 1], vo[2 * i + 1]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) xo[k] = vo[k] = 0u;
-    };
+    typedef XvSink<NWAVE, BURST != 0> Sink;
+    Sink xs(make_xv_win(XV, goff, b, capg, NP, h0, nw, mismatch, has_data), &sh_slot, /* cell */ stage_x + t, /* stride */ TPB,
+            /* burst */ xc);
+    VsCompactor<Sink> vs(xs);
     auto flush_v = [&]() {                   // BURST: the staged quadruples of the called plane
         if (has_data)
             for (int q = 0; q < nq; ++q) {
@@ -949,34 +980,6 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
                 for (int k = 0; k < VN; ++k) o[k] = stage_v[(q * VN + k) * TPB + t];
             }
         nq = 0;
-    };
-    auto finish_dword = [&](int qd) {        // 8 entries (nibbles of cur[k]) -> bits 4j+qd of the two planes
-        const uint32_t nME = ~ME;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const uint32_t cx = (((cur[k] & MA) + 0x77777777u) >> 3) & 0x11111111u;
-            const uint32_t cv = (((cur[k] & nME) + 0x77777777u) >> 3) & 0x11111111u;
-            xo[k] |= cx << qd;
-            vo[k] |= cv << qd;
-            cur[k] = 0u;
-        }
-        MA = 0u;
-        ME = 0u;
-    };
-    auto append = [&](const uint32_t (&Rq)[8], int j, uint32_t A, uint32_t E) {       // j, A, E uniform
-        const int sh = 4 * (cnt & 7);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) cur[k] |= __builtin_amdgcn_ubfe(Rq[k], 4 * j, 4) << sh;
-        MA |= A << sh;
-        ME |= E << sh;
-        ++cnt;
-        if ((cnt & 7) == 0) {
-            finish_dword((cnt >> 3) - 1);
-            if (cnt == 32) {
-                store_word();
-                cnt = 0;
-            }
-        }
     };
     uint32_t dn[32];
 #pragma unroll
@@ -1007,62 +1010,8 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
                 uint32_t pr[4];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) pr[a] = pa[a];
-                wave_or4(pr);
-                if (NWAVE > 1) {
-                    if (lane == 0) {
-#pragma unroll
-                        for (int a = 0; a < 4; ++a) sh_pres[parity][threadIdx.x >> 6][a] = pr[a];
-                    }
-                    __syncthreads();
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) {
-                        uint32_t x = 0u;
-#pragma unroll
-                        for (int wv = 0; wv < NWAVE; ++wv) x |= sh_pres[parity][wv][a];
-                        pr[a] = __builtin_amdgcn_readfirstlane(x);
-                    }
-                    parity ^= 1;
-                }
-                const uint32_t m0 = poly_mask(pr);
-                if (m0) {
-                    // lane l (mod 32) works out the presence nibble of the site at mask bit l and its lowest allele, so that the
-                    // scalar loop below fetches them with one v_readlane per entry instead of a dozen scalar bit operations
-                    const int lb = lane & 31;
-                    const uint32_t Pl = __builtin_amdgcn_ubfe(pr[0], lb, 1) | (__builtin_amdgcn_ubfe(pr[1], lb, 1) << 1) |
-                                        (__builtin_amdgcn_ubfe(pr[2], lb, 1) << 2) | (__builtin_amdgcn_ubfe(pr[3], lb, 1) << 3);
-                    const uint32_t A0l = Pl & (0u - Pl);
-                    auto nib = [&](int bit) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)Pl, bit); };
-                    // virtual site 0 of every polymorphic site: tests the lowest allele present, excludes nothing
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        uint32_t mq = m0 & (0x11111111u << q);
-                        while (mq) {
-                            const int bit = __builtin_ctz(mq);
-                            mq &= mq - 1u;
-                            append(R[q], bit >> 2, (uint32_t)__builtin_amdgcn_readlane((int)A0l, bit), 0u);
-                        }
-                    }
-                    // rare: the second / third virtual site of the sites with three / four alleles
-                    const uint32_t m3 = tri_mask(pr);
-                    if (m3) {
-#pragma unroll 1
-                        for (int pass = 1; pass < 3; ++pass) {
-                            uint32_t m = pass == 1 ? m3 : quad_mask(pr);
-                            while (m) {
-                                const int bit = __builtin_ctz(m);
-                                m &= m - 1u;
-                                const uint32_t P = nib(bit);
-                                const uint32_t A0 = P & (0u - P), P1 = P ^ A0, A1 = P1 & (0u - P1), P2 = P1 ^ A1, A2 = P2 & (0u - P2);
-                                const uint32_t A = pass == 1 ? A1 : A2;
-                                const int q = bit & 3;                        // uniform
-                                if (q == 0) append(R[0], bit >> 2, A, (A - 1u) & P);
-                                else if (q == 1) append(R[1], bit >> 2, A, (A - 1u) & P);
-                                else if (q == 2) append(R[2], bit >> 2, A, (A - 1u) & P);
-                                else append(R[3], bit >> 2, A, (A - 1u) & P);
-                            }
-                        }
-                    }
-                }
+                block_or4<NWAVE>(pr, sh_pres, parity, lane);
+                emit_poly_sites(pr, R, vs, lane);
             }
         }
         if (BURST) {
@@ -1085,11 +1034,10 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
             }
         }
     }
-    if (cnt & 7) finish_dword(cnt >> 3);
-    if (cnt) store_word();
+    vs.finish();
     if (BURST) {
         flush_v();
-        flush_x();
+        xs.flush();
     }
     if (DIP && bad) atomicOr(mismatch, 1);
 }
