@@ -159,6 +159,17 @@ SIGNATURES = {
     "pg_set_deferred_results": (C.c_int, [_P, C.c_int]),
     "pg_results_wait": (C.c_int, [_P]),
     "pg_site_target": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "pg_sfs_begin": (C.c_int, [_P, C.c_int, _i32p, C.c_int, _i32p, _i32p, C.c_int, _i64p, _i32p]),
+    "pg_sfs_add_sites": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_uint64, _i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "pg_sfs_add_base_counts": (C.c_int, [_P, _i32p, C.c_int64, C.c_int, C.c_uint64, _i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "pg_sfs_add_target_counts": (C.c_int, [_P, _i32p, C.c_int64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(C.c_double)]),
+    "pg_sfs_read": (C.c_int, [_P, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "pg_sfs_end": (C.c_int, [_P]),
+    "pg_sfs_target_base": (C.c_int, [_i64p, C.c_void_p, C.POINTER(C.c_int)]),
+    "pg_sfs_time_site_counts": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_double)]),
     "pg_kernel_time": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "pg_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "pg_host_free": (C.c_int, [C.c_void_p]),

@@ -158,6 +158,7 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
     (void)hipStreamSynchronize(c->stream2);
     (void)hipStreamSynchronize(c->stream_up);
     pg_comm_destroy(c);
+    (void)pg_sfs_end(c);
     for (int k = 0; k < 2; ++k) {
         c->slot[k].Vp.release();
         c->slot[k].XV.release();

@@ -236,6 +236,7 @@ struct pg_ctx {
     DevBuf<double> site_val;       // pg_site_target: the finished columns (float64 or int64, 8 bytes either way)
     DevBuf<uint8_t> site_keep;     //                 and the rows' keep flags
     DevBuf<uint32_t> site_flags;   // pg_popfreq: one bit per site (k_popfreq_ordered)
+    void *sfs = nullptr;           // pg_sfs_begin .. pg_sfs_end: the spectra's tables and staging (pg_sfs.hip owns the type)
     // pi / dxy / Fst in NumPy's summation order (k_popdist_np): the reference's row order within the populations and the rank of
     // the population names (pg_set_reference_order; identity until set), the pairwise-summation trees of the block lengths
     DevBuf<int32_t> ref_row, pop_rank, np_trees, np_task_tree;

@@ -12,6 +12,7 @@
 // Integer work is exact; float64 work is compiled with -ffp-contract=off so the per-site products are the
 // same IEEE operations, in the same order, as the NumPy expressions of the reference.
 #include "pg_internal.h"
+#include "pg_range_counts.h"
 #include <algorithm>
 #ifdef PG_DIV_PROBE
 #include <cstdio>
@@ -948,33 +949,7 @@ void pg_launch_indpair_fin(hipStream_t st, const int32_t *Cmat, const int32_t *D
 // `row` = the site's RS/4 dwords of a resident row (8 slots per dword, pg_nib.h); only the first and last dword of a range need
 // a mask.
 // ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void count_dword(uint32_t v, uint32_t cnt[4]) {
-    cnt[0] += __popc(v & 0x11111111u);
-    cnt[1] += __popc(v & 0x22222222u);
-    cnt[2] += __popc(v & 0x44444444u);
-    cnt[3] += __popc(v & 0x88888888u);
-}
-
-// nibble masks of the first / last dword of the slot range [s,e) (e > s)
-__device__ __forceinline__ uint32_t nib_mask_first(int s) { return ~0u << (4 * (s & 7)); }
-__device__ __forceinline__ uint32_t nib_mask_last(int e) {
-    const int hi = ((e - 1) & 7) + 1;
-    return hi == 8 ? 0xFFFFFFFFu : ((1u << (4 * hi)) - 1u);
-}
-
-__device__ __forceinline__ void range_counts(const uint32_t *__restrict__ row, int s, int e, uint32_t cnt[4]) {
-    cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0u;
-    if (e <= s) return;
-    const int d0 = s >> 3, d1 = (e - 1) >> 3;
-    const uint32_t m_first = nib_mask_first(s), m_last = nib_mask_last(e);
-    if (d0 == d1) {
-        count_dword(row[d0] & m_first & m_last, cnt);
-        return;
-    }
-    count_dword(row[d0] & m_first, cnt);
-    for (int d = d0 + 1; d < d1; ++d) count_dword(row[d], cnt);
-    count_dword(row[d1] & m_last, cnt);
-}
+// (count_dword, nib_mask_first / nib_mask_last and range_counts: pg_range_counts.h, shared with pg_sfs.hip)
 
 // ------------------------------------------------------------------------------------------------------
 // K_abba: grid (chunk, window).  Per-site terms follow genomics.py:1409-1475 and 1565-1569 operation for operation;

@@ -477,6 +477,82 @@ class Engine:
                                     int(n_dip), int(n_pops_gen), np.ascontiguousarray(slot_gen_hap, dtype=np.int32),
                                     int(var_thr), int(miss_thr)))
 
+    # ---- site-frequency spectra (pg_sfs.hip; the sfs.py drop-in, genomics_general_amd/sfs.py) -----------------------------------
+    def sfs_begin(self, pop_ext, groups, n_intervals=1):
+        """a spectrum session (pg_sfs_begin): pop_ext[k] = haplotype slots + 1 of ingroup population k, groups = lists of 1 to 4
+        indices into that list.  Returns (cells per group, whether the group is counted in LDS tables)."""
+        ext = np.ascontiguousarray(pop_ext, dtype=np.int32)
+        nd = np.array([len(g) for g in groups], dtype=np.int32)
+        assert len(groups) >= 1 and nd.min() >= 1 and nd.max() <= 4, "a spectrum takes one to four populations"
+        gp = np.zeros((len(groups), 4), dtype=np.int32)
+        for k, g in enumerate(groups):
+            gp[k, :len(g)] = g
+        cells, on_lds = np.zeros(len(groups), dtype=np.int64), np.zeros(len(groups), dtype=np.int32)
+        check(self._L.pg_sfs_begin(self._h, len(ext), ext, len(groups), nd, gp, int(n_intervals), cells, on_lds))
+        self._sfs_ni = int(n_intervals)
+        return cells, on_lds.astype(bool)
+
+    @staticmethod
+    def _sfs_members(members, n):
+        """membership arguments of the add calls: None, or (run_off, iv_start, iv_end, iv_id, row_run, pos) (sfs.Membership.lists +
+        the rows' runs and positions)"""
+        if members is None:
+            return (0, None, None, None, None, None, None), None
+        run_off, st, en, ids, row_run, pos = members
+        keep = [np.ascontiguousarray(run_off, dtype=np.int32), np.ascontiguousarray(st, dtype=np.int64), np.ascontiguousarray(en, dtype=np.int64),
+                np.ascontiguousarray(ids, dtype=np.int32), np.ascontiguousarray(row_run, dtype=np.int32), np.ascontiguousarray(pos, dtype=np.int64)]
+        assert len(keep[4]) == n and len(keep[5]) == n and len(keep[1]) == len(keep[2]) == len(keep[3]) == keep[0][-1]
+        return (len(keep[0]) - 1,) + tuple(C.c_void_p(a.ctypes.data) for a in keep), keep
+
+    def sfs_add_sites(self, site_lo, site_hi, ord0, in_pops, out_pop=-1, members=None):
+        """resident rows [site_lo, site_hi) into the spectra (k_sfs_rows); returns the launches' HIP-event milliseconds"""
+        m, _keep = self._sfs_members(members, int(site_hi) - int(site_lo))
+        ms = C.c_double(0.0)
+        check(self._L.pg_sfs_add_sites(self._h, int(site_lo), int(site_hi), int(ord0), np.ascontiguousarray(in_pops, dtype=np.int32), int(out_pop),
+                                       *m, C.byref(ms)))
+        return ms.value
+
+    def sfs_add_base_counts(self, cnt, ord0, in_cols, out_col=-1, members=None):
+        """int32 [n][n_cols][4] base counts into the spectra (k_sfs_base)"""
+        cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+        assert cnt.ndim == 3 and cnt.shape[2] == 4
+        m, _keep = self._sfs_members(members, len(cnt))
+        ms = C.c_double(0.0)
+        check(self._L.pg_sfs_add_base_counts(self._h, cnt, len(cnt), cnt.shape[1], int(ord0), np.ascontiguousarray(in_cols, dtype=np.int32),
+                                             int(out_col), *m, C.byref(ms)))
+        return ms.value
+
+    def sfs_add_target_counts(self, tc, ord0, members=None):
+        """int32 [n][n_in] target counts into the spectra (k_sfs_target)"""
+        tc = np.ascontiguousarray(tc, dtype=np.int32)
+        assert tc.ndim == 2
+        m, _keep = self._sfs_members(members, len(tc))
+        ms = C.c_double(0.0)
+        check(self._L.pg_sfs_add_target_counts(self._h, tc, len(tc), int(ord0), *m, C.byref(ms)))
+        return ms.value
+
+    def sfs_read(self):
+        """the touched cells (k_sfs_compact), in no particular order: (cell index over the groups' tables laid end to end, first line
+        ordinal, counts [n][n_intervals])"""
+        n = C.c_int64(0)
+        check(self._L.pg_sfs_read(self._h, 0, None, None, None, C.byref(n)))
+        k = int(n.value)
+        cell, first, counts = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.uint64), np.zeros((k, self._sfs_ni), dtype=np.uint64)
+        if k:
+            check(self._L.pg_sfs_read(self._h, k, C.c_void_p(cell.ctypes.data), C.c_void_p(first.ctypes.data), C.c_void_p(counts.ctypes.data),
+                                      C.byref(n)))
+            assert n.value == k
+        return cell, first, counts
+
+    def sfs_end(self):
+        check(self._L.pg_sfs_end(self._h))
+
+    def time_site_counts(self, site_lo, site_hi):
+        """HIP-event milliseconds of k_site_counts alone over resident rows (tools/sfs_bench.py)"""
+        ms = C.c_double(0.0)
+        check(self._L.pg_sfs_time_site_counts(self._h, int(site_lo), int(site_hi), C.byref(ms)))
+        return ms.value
+
     def sync(self):
         check(self._L.pg_sync(self._h))
 

@@ -517,6 +517,43 @@ int pg_site_counts(pg_ctx *ctx, int64_t site_lo, int64_t site_hi, int32_t *cnt_o
 int pg_site_target(pg_ctx *ctx, int64_t site_lo, int64_t site_hi, int target, double min_data, int as_counts, int has_threshold,
                    double threshold, void *values_out, uint8_t *keep_out);
 
+/* ---- site-frequency spectra (the sfs.py drop-in, cli.sfs_main; pg_sfs.hip) --------------------------------------------------------
+ * Replaces sfs.py:428-496 (the per-site loop: completeness, getTargetCounts, SparseFS.add) for every spectrum at once.  A session:
+ * pg_sfs_begin, any number of pg_sfs_add_*, pg_sfs_read, pg_sfs_end (pg_ctx_destroy ends an open one).
+ * pg_sfs_begin: n_in ingroup populations with extents pop_ext[k] (haplotype slots + 1; a target count must stay below it); n_groups
+ * spectra of group_nd[g] (1 to 4) populations group_pops[g][4] (indices into the ingroup list, the first the most significant digit
+ * of the cell index); n_intervals counts per cell (1 without regions).  Per group a dense table count[cell][n_intervals] (u64) and
+ * first[cell] (u64, the lowest line ordinal that touched the cell, all-ones when none did); their total size is held against the
+ * scratch budget (PG_SCRATCH_GIB, pg_set_scratch_limit) before anything is allocated.  cells_out[n_groups] / on_lds_out[n_groups] (may
+ * be NULL): cells per group, and whether the group is counted in LDS tables (PG_SFS_LDS=0: none is).  PG_SFS_CHUNK: sites per launch.
+ * Membership of the add calls: n_runs == 0: every row counts, for interval 0.  Otherwise row i belongs to run row_run[i] and has
+ * position pos[i]; run r lists the inclusive intervals [iv_start[j], iv_end[j]] -> interval id iv_id[j], j in [run_off[r],
+ * run_off[r+1]); a row adds 1 per list entry that holds its position and is left out when none does.
+ * ord0: the line ordinal of the call's first row (row i has ord0 + i).  ms_out (may be NULL): HIP-event time of the launches. */
+int pg_sfs_begin(pg_ctx *ctx, int n_in, const int32_t *pop_ext, int n_groups, const int32_t *group_nd, const int32_t *group_pops,
+                 int n_intervals, int64_t *cells_out, int32_t *on_lds_out);
+/* resident rows [site_lo, site_hi): in_pops[n_in] populations of pg_set_samples, out_pop the outgroup (-1: the minor allele). */
+int pg_sfs_add_sites(pg_ctx *ctx, int64_t site_lo, int64_t site_hi, uint64_t ord0, const int32_t *in_pops, int out_pop, int n_runs,
+                     const int32_t *run_off, const int64_t *iv_start, const int64_t *iv_end, const int32_t *iv_id, const int32_t *row_run,
+                     const int64_t *pos, double *ms_out);
+/* cnt[n][n_cols][4] base counts (a freq.py table): in_cols[n_in] / out_col are columns; no completeness test (sfs.py:464-479). */
+int pg_sfs_add_base_counts(pg_ctx *ctx, const int32_t *cnt, int64_t n, int n_cols, uint64_t ord0, const int32_t *in_cols, int out_col,
+                           int n_runs, const int32_t *run_off, const int64_t *iv_start, const int64_t *iv_end, const int32_t *iv_id,
+                           const int32_t *row_run, const int64_t *pos, double *ms_out);
+/* tc[n][n_in] counts of the target allele (sfs.py:481-483). */
+int pg_sfs_add_target_counts(pg_ctx *ctx, const int32_t *tc, int64_t n, uint64_t ord0, int n_runs, const int32_t *run_off,
+                             const int64_t *iv_start, const int64_t *iv_end, const int32_t *iv_id, const int32_t *row_run, const int64_t *pos,
+                             double *ms_out);
+/* The touched cells, in no particular order: *n_out their number; with cap > 0 the first min(cap, n) of them as cell_out (index into
+ * the groups' tables laid end to end), first_out, count_out[.][n_intervals].  cap == 0 only counts. */
+int pg_sfs_read(pg_ctx *ctx, int64_t cap, int64_t *cell_out, uint64_t *first_out, uint64_t *count_out, int64_t *n_out);
+int pg_sfs_end(pg_ctx *ctx);
+/* The target allele of a site from the ingroup's totals tot4 and the outgroup's counts out4 (NULL: the minor allele, NumPy's
+ * argsort()[-2] with its tie order): the device function, callable on the host.  *base_out = -1 for a site that is left out. */
+int pg_sfs_target_base(const int64_t *tot4, const int64_t *out4, int *base_out);
+/* k_site_counts alone over resident rows, HIP-event time without the copy to the host (tools/sfs_bench.py's yardstick). */
+int pg_sfs_time_site_counts(pg_ctx *ctx, int64_t site_lo, int64_t site_hi, double *ms_out);
+
 /* ---- per-haplotype called-site counts ------------------------------------------------------------ */
 /* Replaces Alignment.seqNonNan (genomics.py:1038-1040) as used by distMat.py:40 (--minPerInd):
  * called_out[n_win][n_hap] = number of sites of the window at which the haplotype slot is called. */
