@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import deflate_craft as craft  # noqa: E402
 from genomics_general_amd import genoio, vcf  # noqa: E402
 from genomics_general_amd.engine import Engine  # noqa: E402
 
@@ -84,6 +85,33 @@ def test_members_inflate_to_the_text(eng, what):
         assert len(comp) <= len(text) + (len(text) // 65280 + 1) * 31          # stored members: five bytes of block header + 26 of gzip
     if what in ("zeros", "acgt"):
         assert len(comp) < len(text) // 100
+
+
+_depths = {}
+
+
+@pytest.mark.parametrize("name", craft.SKEWED_NAMES)
+def test_codes_deeper_than_the_format_allows_are_limited(eng, name):
+    """df_code_lengths limits a code to 15 bits (7 for the code-length code) by moving leaves as miniz does.  Texts whose frequencies
+    make an unrestricted Huffman code deeper (tests/deflate_craft.py: skewed_texts) through _check, then member 0 as the walker sees
+    it: every length within the limit, every code complete.
+    Measured on an MI355X, unrestricted depth of the frequencies k_deflate coded -> longest code it wrote: literal / length code 15 ->
+    15 (fibonacci_22_symbols: 10 970 matches absorb most of the text), 15 -> 15 (fibonacci_24_symbols), 20 -> 15
+    (fibonacci_tail_without_matches); code-length code 9 -> 7 (code_length_fibonacci); 6 -> 6 for the code-length code of the other three."""
+    kind, text = [(k, t) for n, k, t in craft.skewed_texts() if n == name][0]
+    comp = _check(eng, text)
+    tab, _, _ = genoio.bgzf_walk(comp, None, 1 << 40)
+    facts = craft.dynamic_block_facts(comp[int(tab[0][0]):int(tab[0][0]) + int(tab[1][0])])
+    print("[deflate] %s: %r" % (name, facts))
+    _depths[name] = (kind, facts)
+
+
+def test_the_skewed_texts_did_need_limiting():
+    """the premise of the test above: for at least one text of each kind the frequencies k_deflate coded have an unrestricted
+    Huffman depth beyond the limit (what its match finder leaves of a text's frequencies is its own business)"""
+    assert len(_depths) == len(craft.SKEWED_NAMES), "run together with test_codes_deeper_than_the_format_allows_are_limited"
+    assert max(f["ll"] for kind, f in _depths.values() if kind == "ll") > 15
+    assert max(f["cl"] for kind, f in _depths.values() if kind == "cl") > 7
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("PG_DEFLATE_FUZZ_SEEDS", "60"))))

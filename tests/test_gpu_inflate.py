@@ -19,6 +19,7 @@ from golden_util import align_columns
 from genomics_general_amd import _lib, genoio
 from genomics_general_amd.engine import Engine
 
+import deflate_craft as craft
 import test_gpu_golden as G
 from test_cli_cpu import write_bgzf
 
@@ -138,6 +139,38 @@ def test_a_damaged_member_is_named_not_inflated(engine, damage):
         device_inflate(engine, data)
     got, _ = device_inflate(engine, b"".join(good))                         # the context is as usable as before
     assert zlib.crc32(got) == zlib.crc32(b"".join(zlib.decompress(g[18:-8], wbits=-15) for g in good))
+
+
+# ---- streams zlib never writes (tests/deflate_craft.py; tests/test_inflate.py has held the emulation and the sanitizer program against
+# the same corpus on the CPU before any of it reaches the device) ----
+def test_members_only_other_writers_deflate_inflate_to_what_zlib_gives(engine):
+    """codes of 15 bits, every length and distance symbol, distance 32 768, 258 as symbol 284, header runs across the boundary of the
+    two sets of lengths, one-bit distance codes, stored blocks at every bit phase, 300 blocks in a member, the ring sweep (a far
+    match reads global memory the same wave flushed moments before: only the device can show that): all in ONE launch, CRC on"""
+    legal, _ = craft.checked_streams()
+    data = b"".join(craft.wrap_member(m["raw"], m["text"]) for m in legal) + EOF_MEMBER
+    got, ms = device_inflate(engine, data)
+    want = b"".join(m["text"] for m in legal)
+    assert len(got) == len(want)
+    at = 0
+    for k, m in enumerate(legal):
+        if got[at:at + len(m["text"])] != m["text"]:
+            raise AssertionError("member %d (%s) is the first that differs from zlib's text" % (k, m["name"]))
+        at += len(m["text"])
+    print("[inflate] %d crafted members, %.2f MB of text in %.3f ms" % (len(legal), len(want) / 1e6, ms))
+
+
+@pytest.mark.parametrize("name", craft.ILLEGAL_NAMES)
+def test_a_member_zlib_refuses_is_named_not_inflated(engine, name):
+    _, illegal = craft.checked_streams()
+    bad = [m for m in illegal if m["name"] == name][0]
+    rng = random.Random(11)
+    good = [member(geno_text(rng, 60, 40)) for _ in range(5)]
+    data = b"".join(good[:3] + [craft.wrap_member(bad["raw"], bytes(bad["out_len"]))] + good[4:])
+    with pytest.raises(_lib.PopgenError, match="damaged BGZF member \\(member 3 of the block"):
+        device_inflate(engine, data)
+    got, _ = device_inflate(engine, b"".join(good))                         # the context is as usable as before
+    assert got == b"".join(zlib.decompress(g[18:-8], wbits=-15) for g in good)
 
 
 BGZF_CASES = [c for c in G.STREAMABLE if c["fixture"] != "mixed"]

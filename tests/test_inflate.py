@@ -19,6 +19,8 @@ import pytest
 
 from genomics_general_amd import genoio
 
+import deflate_craft as craft
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -170,6 +172,141 @@ def test_damaged_streams_end_in_an_error_and_touch_nothing_outside_their_output(
             assert rc != 0
             err += 1
     assert agree > 500 and err > 500
+
+
+# ---- streams zlib never writes (tests/deflate_craft.py) ----------------------------------------------------------------------------
+def test_the_crafted_corpus_is_what_it_says():
+    """zlib accepts every legal stream to its last bit with the text the writer meant and refuses every illegal one (checked_streams);
+    the walker reads the same text out of the legal ones; the facts the corpus is built for hold: codes of 15 bits, runs of the
+    header that start in the literal / length lengths and end in (or, where the format allows no more, at) the distance lengths,
+    length 258 as symbol 284, distance 32 768, every length and distance symbol, stored blocks at all eight bit phases"""
+    legal, illegal = craft.checked_streams()
+    assert [m["name"] for m in illegal] == craft.ILLEGAL_NAMES
+    assert all(len(m["text"]) <= 65280 and len(m["raw"]) <= 65536 - 26 for m in legal)
+    lsyms, dsyms, phases, far, as_284 = set(), set(), set(), 0, 0
+    for m in legal:
+        blocks = craft.walk(m["raw"])
+        assert craft.walked_text(blocks) == m["text"], m["name"]
+        for b in blocks:
+            for t in b["tokens"]:
+                if not isinstance(t, int):
+                    lsyms.add(t[2])
+                    dsyms.add(t[3])
+                    far += t[1] == 32768
+                    as_284 += t[0] == 258 and t[2] == 284
+        if m["group"] == "a":
+            assert sorted(n for n in blocks[0]["ll_lens"] if n) == list(range(1, 16)) + [15] and blocks[0]["ll_lens"][256] == 15
+            assert blocks[0]["hdist"] == 1 and blocks[0]["d_lens"] == [0] and min(blocks[0]["tokens"].count(s) for s in set(blocks[0]["tokens"])) >= 20
+        if m["group"] == "b":
+            assert all(blocks[0]["ll_lens"]) and sorted(blocks[0]["d_lens"]) == list(range(1, 11)) + [14] * 12 + [15] * 8
+        if m["group"] == "c":
+            kind, (lo, hi) = m["run"]
+            assert any(s == kind and at <= lo and at + n - 1 >= hi for s, at, n in blocks[0]["ops"]), (m["name"], blocks[0]["ops"])
+            assert (blocks[0]["hlit"], blocks[0]["hdist"]) == tuple(int(x) for x in m["name"].split("_")[5::2])
+        if m["group"] == "f":
+            k = [b["type"] for b in blocks].index("stored")
+            assert [b["type"] for b in blocks] == ["fixed", "fixed", "dynamic", "fixed", "stored", "stored", "stored", "fixed", "dynamic", "stored"]
+            n_pad = (5 - int(m["name"][-1])) % 8
+            assert blocks[k]["pad"] == (1 << n_pad) - 1 and blocks[k + 1]["pad"] == 31 and len(blocks[k + 1]["data"]) == 3000 + int(m["name"][-1])
+            phases.add(int(m["name"][-1]))
+        if m["group"] == "g":
+            assert len(blocks) == 300 and [b["type"] for b in blocks[:3]] == ["stored", "fixed", "dynamic"]
+    assert lsyms == set(range(257, 286)) and dsyms == set(range(30)) and phases == set(range(8)) and far >= 3 and as_284 >= 30
+    crossing = [m for m in legal if m["group"] == "c" and m["run"][1][1] >= int(m["name"].split("_")[5])]
+    assert {m["run"][0] for m in crossing} == {16, 18} and len(crossing) == 4
+
+
+def test_the_kernel_source_inflates_what_only_other_writers_deflate(emul):
+    """the legal streams of the corpus through the lockstep emulation of k_inflate, CRC check on, the list of line feeds on where the
+    text has any: zlib's bytes, zlib's line feeds, nothing touched outside the output -- at misalignments 0, 7 and 15 of the output;
+    at all sixteen for the deep code, the ring sweep and the block mix (the flush in aligned pieces sees the ring at every offset)"""
+    legal, _ = craft.checked_streams()
+    rng = random.Random(17)
+    n = 0
+    for m in legal:
+        text, want = m["text"], [i for i, ch in enumerate(m["text"]) if ch == 10]
+        for mis in (range(16) if m["group"] in "aef" else (0, 7, 15)):
+            n += 1
+            if want:
+                rc, out, cnt, offs = emul(m["raw"], len(text), pre=n % 9, post=n % 5, misalign=mis, rng=rng, nl=(70000, 0xFFFFFFFF), crc=zlib.crc32(text))
+                assert rc == 0 and out == text and cnt == len(want) and offs == want, (m["name"], mis, rc)
+            else:
+                rc, out = emul(m["raw"], len(text), pre=n % 9, post=n % 5, misalign=mis, rng=rng, crc=zlib.crc32(text))
+                assert rc == 0 and out == text, (m["name"], mis, rc)
+    assert n > 400 and sum(10 in m["text"] for m in legal) > 30
+
+
+def test_the_kernel_source_refuses_what_zlib_refuses(emul):
+    """the illegal streams of the corpus through the emulation: an error, and the canaries around the output intact (rc < 2^20)"""
+    _, illegal = craft.checked_streams()
+    rng = random.Random(18)
+    for m in illegal:
+        for mis in range(16):
+            for crc in (None, zlib.crc32(bytes(m["out_len"]))):
+                rc, _ = emul(m["raw"], m["out_len"], pre=mis % 9, post=mis % 5, misalign=mis, rng=rng, crc=crc)
+                assert rc != 0 and rc < (1 << 20), (m["name"], mis, rc)
+
+
+def test_the_host_decoders_on_the_crafted_corpus(tmp_path):
+    """genoio.bgzf_inflate (a BGZF member) and GzipStream (a one-member gzip file; pg_fast_inflate.h's tables are 11 bits wide, so the
+    code of group a and the distance code of group b go through its second-level tables) give zlib's bytes for every legal stream
+    and raise for every illegal one"""
+    legal, illegal = craft.checked_streams()
+    path = str(tmp_path / "c.gz")
+
+    def stream_text(want):
+        rd = genoio.GzipStream(path)
+        assert rd._L.pg_gzip_open is not None
+        got = b""
+        while True:
+            b = bytes(rd.read_lines(want))
+            if not b:
+                break
+            got += b
+        rd.close()
+        return got
+    for m in legal:
+        member = craft.wrap_member(m["raw"], m["text"])
+        tab, used, n_text = genoio.bgzf_walk(member)
+        assert used == len(member) and n_text == len(m["text"])
+        assert genoio.bgzf_inflate(member, tab).tobytes() == m["text"], m["name"]
+        with open(path, "wb") as f:
+            f.write(craft.wrap_gzip(m["raw"], m["text"]))
+        for want in (1 << 30, 1000, 33333):
+            assert stream_text(want) == m["text"], (m["name"], want)
+    for m in illegal:
+        member = craft.wrap_member(m["raw"], bytes(m["out_len"]))
+        tab, used, _ = genoio.bgzf_walk(member)
+        assert used == len(member)
+        with pytest.raises(ValueError, match="damaged BGZF member"):
+            genoio.bgzf_inflate(member, tab)
+        with open(path, "wb") as f:
+            f.write(craft.wrap_gzip(m["raw"], bytes(m["out_len"])))
+        for want in (1 << 30, 1000):
+            with pytest.raises(Exception, match="invalid deflate data|ends inside a member"):
+                stream_text(want)
+
+
+def test_the_kernel_source_under_sanitizers_as_a_program_of_its_own(tmp_path):
+    """tests/inflate_emul_main.cpp + tests/inflate_emul.cpp built with AddressSanitizer and UndefinedBehaviorSanitizer and run as a
+    program on the whole corpus (legal and illegal, three misalignments each): an index past an array of the emulated LDS, a read
+    behind the member's bytes, a shift by a negative count would end it"""
+    legal, illegal = craft.checked_streams()
+    corpus = str(tmp_path / "corpus.bin")
+    with open(corpus, "wb") as f:
+        f.write(struct.pack("<I", len(legal) + len(illegal)))
+        for m in legal:
+            f.write(struct.pack("<III", len(m["raw"]), len(m["text"]), 0) + m["raw"] + m["text"])
+        for m in illegal:
+            f.write(struct.pack("<III", len(m["raw"]), m["out_len"], 1) + m["raw"] + bytes(m["out_len"]))
+    exe = str(tmp_path / "inflate_emul_main")
+    # (the runtimes linked statically: the program is complete in itself, whatever else the environment loads into a process)
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+                           "-static-libubsan", os.path.join(ROOT, "tests", "inflate_emul.cpp"), os.path.join(ROOT, "tests", "inflate_emul_main.cpp"),
+                           "-o", exe])
+    r = subprocess.run([exe, corpus], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0, (r.returncode, r.stdout.decode()[-500:], r.stderr.decode()[-3000:])
+    assert r.stdout.decode().strip() == "%d runs, 0 bad" % (3 * (len(legal) + len(illegal)))
 
 
 # ---- host side --------------------------------------------------------------------------------------------------------------------
@@ -507,12 +644,23 @@ def test_the_host_compressor_round_trips_through_zlib_and_the_decoders(tmp_path)
     for p in (1, 2, 3, 5, 8, 13, 255, 256, 257, 4000, 32767, 32768, 32769, 40000):
         pat = bytes(rng.randrange(256) for _ in range(p))
         texts.append((pat * (200000 // p + 2))[:200000])
+    skewed = craft.skewed_texts()              # frequencies whose Huffman codes need limiting (tests/test_gpu_deflate.py: k_deflate on the same)
+    texts += [t for _, _, t in skewed]
     for text in texts:
         for block in (65280, 4097, 65535 if len(text) % 2 else 1000):
             bz = genoio.bgzf_compress(text, block=min(block, 65280))
             assert gzip.decompress(bz.tobytes()) == text, (len(text), block)
             tab, used, n_text = genoio.bgzf_walk(bz)
             assert n_text == len(text) and genoio.bgzf_inflate(bz, tab).tobytes() == text
+    # ... and the limiting itself: the codes of member 0 stay within 15 (7) bits and complete, where an unrestricted Huffman code of the
+    # frequencies the compressor coded is deeper (measured: 14, 14, 20 for the literal / length code, 9 for the code-length code)
+    depth = {}
+    for name, kind, text in skewed:
+        bz = genoio.bgzf_compress(text).tobytes()
+        tab, _, _ = genoio.bgzf_walk(bz)
+        depth[name] = craft.dynamic_block_facts(bz[int(tab[0][0]):int(tab[0][0]) + int(tab[1][0])])
+    print("[host deflate] " + ", ".join("%s: %r" % kv for kv in depth.items()))
+    assert max(d["ll"] for n, d in depth.items() if n.startswith("fibonacci")) > 15 and depth["code_length_fibonacci"]["cl"] > 7
     g = geno_text(rng, 6000, 100)
     own = len(genoio.bgzf_compress(g))
     z6 = sum(len(zlib.compress(g[a:a + 65280], 6)) + 14 for a in range(0, len(g), 65280))
