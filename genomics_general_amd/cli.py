@@ -1929,3 +1929,123 @@ def sfs_main(argv=None):
     """Drop-in for the reference's sfs.py (sfs.py:161-505): the spectra are counted by k_sfs_rows / k_sfs_base / k_sfs_target"""
     from . import sfs
     return sfs.main(argv)
+
+
+# ==========================================================================================================
+# distPaint.py  (per window and individual: the nearest reference population; distPaint.py:26-87, 157-259)
+# ==========================================================================================================
+@guarded_main
+def distpaint_main(argv=None):
+    """Drop-in for the reference's distPaint.py: D and C of every window from the pack and pair kernels, the decision by k_paint
+    (engine.WindowBatch.paint).  Every column of the file is a haploid individual (distPaint.py:257-259)."""
+    ap = argparse.ArgumentParser(prog="distPaint.py", epilog=ENGINE_EPILOG)
+    _add(ap, WINDOW_FLAGS, **{"--windType": dict(choices=("sites", "coordinate", "predefined"))})
+    ap.add_argument("-O", "--overlap", type=int, metavar="sites", help="Overlap for sites sliding window")
+    ap.add_argument("--minData", type=float, metavar="prop", default=0.01, help="accepted and ignored, as in the reference")
+    ap.add_argument("--p_threshold", type=float, default=0.05, help="Maximum p-value to assign to a reference populaton")
+    ap.add_argument("--delta_threshold", type=float, default=None,
+                    help="Alternative method: minimum delta from next best to assign to a reference populaton")
+    ap.add_argument("-p", "--population", action="append", nargs="+", metavar=("popName", "[samples]"),
+                    help="Pop name and optionally sample names (separated by commas)")
+    ap.add_argument("--popsFile", help="Optional file of sample names and populations")
+    ap.add_argument("--samples", metavar="sample names", help="accepted and ignored, as in the reference")
+    ap.add_argument("--noresult", type=int, default=-1, help="Value to use when no population is assigned")
+    ap.add_argument("-g", "--genoFile", required=True, help="Input genotypes file")
+    ap.add_argument("-o", "--outFile", help="Results file (.gz by suffix; stdout if absent)")
+    ap.add_argument("--exclude", help="File of scaffolds to exclude")
+    ap.add_argument("--include", help="File of scaffolds to analyse")
+    ap.add_argument("--header", help="Header text if no header in input")
+    ap.add_argument("-T", "--threads", type=int, default=1, metavar="threads",
+                    help="accepted for compatibility; the GPU engine does not use worker processes")
+    ap.add_argument("--verbose", action="store_true", help="Verbose output")
+    ap.add_argument("--addWindowID", action="store_true", help="Add window name or number as first column")
+    ap.add_argument("--writeFailedWindows", action="store_true", help="Write output even for windows with too few sites.")
+    ap.add_argument("--device", type=int, default=None, help="GPU index (MI355X engine)")
+    args = ap.parse_args(argv)
+    args.genoFormat = "haplo"
+
+    wp = _window_setup(args, args.overlap)
+    minSites = args.minSites
+    if not minSites:
+        if not args.windSize:
+            ap.error("-m 0 stands for the window size: give -w, or a minimum number of sites")
+        minSites = args.windSize
+    if not args.population:
+        ap.error("no reference population: give -p NAME [ind,ind...] (and --popsFile) at least once")
+    # (with --header the reference still takes its names from the file's first line, a data line then: here they are the header's)
+    allInds = args.header.split()[2:] if args.header else genoio.read_header_names(args.genoFile)
+    # reference individuals as FILE COLUMNS, in the order given: -p first, then --popsFile; duplicates kept (distPaint.py:239-255)
+    popNames, refs = [], {}
+    for p in args.population:
+        popNames.append(p[0])
+        refs[p[0]] = []
+        if len(p) > 1:
+            for ind in p[1].split(","):
+                if ind not in allInds:
+                    raise ValueError("%r (population %s) is not in the header of %s" % (ind, p[0], args.genoFile))
+                refs[p[0]].append(allInds.index(ind))
+    if args.popsFile:
+        with open(args.popsFile, "rt") as pf:
+            popDict = dict([ln.split() for ln in pf])
+        for ind, pop in popDict.items():
+            if pop in refs and ind in allInds:               # (a name the file lacks, a population no -p names: skipped)
+                refs[pop].append(allInds.index(ind))
+    for name in popNames:
+        if len(refs[name]) < 1:
+            ap.error("Reference population %s appears to have no individuals." % name)
+    if args.delta_threshold is not None and len(popNames) < 2:
+        ap.error("--delta_threshold compares the two nearest reference populations: give at least two -p")
+    ref_lists = [refs[name] for name in popNames]
+    # The reference's alignment holds the sequences in sorted-name order (genomics.py:1122) and distPaint.py indexes it by file column
+    # (distPaint.py:69, 73, 247): under the k-th name of the header stands the result of the k-th name in sorted order, and a reference
+    # index means that row too.  Reproduced; said once when it makes a difference.
+    if list(np.argsort(np.array(allInds))) != list(range(len(allInds))) and dist.world_from_env().rank == 0:
+        sys.stderr.write("warning: the sample names of the header are not in sorted order: like the reference, the k-th sample column and "
+                         "every reference individual then stand for the k-th name in SORTED order, not for the k-th column\n")
+    sampleData = SampleData(indNames=list(allInds), ploidyDict=dict(zip(allInds, [1] * len(allInds))))
+
+    run = Run(args, sampleData, wp, minSites, header_line=args.header, coords_keep=3, stream=True, shardable=True)
+    n_ind = len(allInds)
+    head = ("windowID\t" if args.addWindowID else "") + "\t".join(["scaffold", "start", "end", "mid", "sites"]) + "\t" + "\t".join(allInds) + "\n"
+    sink = run.open_sink(args.outFile, head, id_column=args.addWindowID, id_sep="\t")
+    nan_cells = "\t".join(["nan"] * n_ind)
+    last_row = None
+    try:
+        for _ in run.chunks():
+            T = run.T
+            good = T.sites[run.w0:run.w1] >= minSites
+            table = np.full((run.w1 - run.w0, n_ind), np.nan)
+            if np.any(good):
+                table[good] = run.batch(good).paint(ref_lists, minSites, p_threshold=args.p_threshold, delta_threshold=args.delta_threshold,
+                                                    noresult=args.noresult)
+            full = run.gather(table)
+            if not sink.local:
+                continue
+            ids, start, end, mid = T.ID, T.start, T.end, T.mid
+            sites, dup = np.asarray(T.sites).tolist(), np.asarray(T.dup).tolist()
+            for k in range(T.n):
+                if dup[k]:
+                    ok, text = last_row
+                else:
+                    ok = sites[k] >= minSites
+                    lead = ([ids[k]] if args.addWindowID else []) + [T.scaffold[k], start[k], end[k], mid[k], int(sites[k])]
+                    cells = "\t".join(map(str, full[k].astype(np.int64).tolist())) if ok else nan_cells
+                    text = "\t".join(map(str, lead)) + "\t" + cells + "\n"
+                    last_row = (ok, text)
+                if ok or args.writeFailedWindows:
+                    sink.write(text)
+    except _lib.PopgenError as exc:
+        if exc.code != _lib.PG_ERR_PARSE:
+            raise
+        # a line that cannot be read as one-character genotypes (the reference's worker dies there -- on its ploidy assertion for a
+        # cell of another width -- and the run hangs)
+        sys.stderr.write("distPaint.py: the input cannot be read as haploid genotypes, ONE character per cell: %s\n" % exc)
+        raise SystemExit(2)
+    tested, written = sink.close()
+    if run.world.rank == 0:
+        sys.stderr.write(str(tested) + " windows were tested.\n")
+        sys.stderr.write(str(written) + " results were written.\n")
+        sys.stderr.write("\nDone.\n")
+    run.report_timing()
+    run.finish()
+    return 0

@@ -159,6 +159,7 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
     (void)hipStreamSynchronize(c->stream_up);
     pg_comm_destroy(c);
     (void)pg_sfs_end(c);
+    c->paint.release();
     for (int k = 0; k < 2; ++k) {
         c->slot[k].Vp.release();
         c->slot[k].XV.release();
@@ -1021,6 +1022,12 @@ static int pairwise_run(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_w
         if ((rc = note_flags(c, flag, &dip, &again)) != PG_OK) return rc;
         if (!again) return PG_OK;
     }
+}
+
+int pg_pairwise_each(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_win, const std::function<int(int, int)> &consume) {
+    int rc = check_windows(c, lo, hi, n_win);
+    if (rc != PG_OK) return rc;
+    return pairwise_run(c, lo, hi, n_win, [&](int w0, int nb) -> int { return consume(w0, nb); });
 }
 
 // ---- placement of the resident rows ---------------------------------------------------------------------------------------------

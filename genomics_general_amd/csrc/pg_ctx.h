@@ -6,6 +6,7 @@
 #include "pg_vcf_core.h"
 #include "pg_filter_core.h"
 
+#include <functional>
 #include <utility>
 #include <vector>
 
@@ -236,6 +237,14 @@ struct pg_ctx {
     DevBuf<double> site_val;       // pg_site_target: the finished columns (float64 or int64, 8 bytes either way)
     DevBuf<uint8_t> site_keep;     //                 and the rows' keep flags
     DevBuf<uint32_t> site_flags;   // pg_popfreq: one bit per site (k_popfreq_ordered)
+    // pg_paint (pg_paint.hip): [individual slots | ref_start | ref_slot], the critical rank sums, a batch's decisions, the cells left to the
+    // host (their number, indices and means)
+    struct Paint {
+        DevBuf<int32_t> tab, out;
+        DevBuf<int64_t> crit, count, cell;
+        DevBuf<double> means;
+        void release() { tab.release(); out.release(); crit.release(); count.release(); cell.release(); means.release(); }
+    } paint;
     void *sfs = nullptr;           // pg_sfs_begin .. pg_sfs_end: the spectra's tables and staging (pg_sfs.hip owns the type)
     // pi / dxy / Fst in NumPy's summation order (k_popdist_np): the reference's row order within the populations and the rank of
     // the population names (pg_set_reference_order; identity until set), the pairwise-summation trees of the block lengths
@@ -280,5 +289,9 @@ struct pg_ctx {
 };
 
 std::vector<PgTask2> pg_make_tasks2(int n, int max_nsub, int diag);
+// the windows through the pack and pair kernels, for entry points outside pg_abi.cpp: the windows are checked, then consume(w0, nb) is
+// called per sub-batch with D / C queued on ctx->stream in ctx->Dmat / ctx->Cmat (pairwise_batches); a pass that the pack kernels' flag
+// word makes start over calls it again from window 0
+int pg_pairwise_each(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_win, const std::function<int(int, int)> &consume);
 int pg_time_begin(pg_ctx *c, int k, hipEvent_t *e0, hipEvent_t *e1);
 int pg_time_end(pg_ctx *c, int k, hipEvent_t e0, hipEvent_t e1, int launches);

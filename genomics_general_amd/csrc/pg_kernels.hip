@@ -410,31 +410,7 @@ void pg_launch_sample_het(hipStream_t st, const int32_t *Cmat, const int32_t *Dm
 //   3. f = sizes / n;  H1 = sum f^2,  H12 = H1 + 2 f0 f1,  H2 = sum_{k>=1} f_k^2  (H12 = H1, H2 = 0 for a single cluster).
 // `order[pop_start[p] .. pop_start[p+1])` = the population's slots in the reference's row order.
 // ------------------------------------------------------------------------------------------------------
-// float64 sum in the order NumPy's add.reduce visits a contiguous array (the reference's `(clusterFreq**2).sum()`,
-// genomics.py:1088-1091): fewer than 8 elements left to right; up to 128 in eight strided partial sums combined as a tree, the
-// tail added one by one; beyond that the range is halved (the first half rounded down to a multiple of 8).
-template <int DEPTH>
-__device__ double np_pairwise_sum(const double *a, int n) {
-    if (n < 8) {
-        double r = 0.0;
-        for (int i = 0; i < n; ++i) r += a[i];
-        return r;
-    }
-    if (n <= 128 || DEPTH == 0) {
-        double r[8];
-        for (int j = 0; j < 8; ++j) r[j] = a[j];
-        int i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += a[i];
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_sum<(DEPTH > 0 ? DEPTH - 1 : 0)>(a, n2) + np_pairwise_sum<(DEPTH > 0 ? DEPTH - 1 : 0)>(a + n2, n - n2);
-}
-
+// (np_pairwise_sum, the float64 sum in NumPy's add.reduce order by one lane: pg_internal.h)
 __global__ __launch_bounds__(256) void k_hapstats(const int32_t *__restrict__ Cmat, const int32_t *__restrict__ Dmat, int N,
                                                   int cN, int cshift, const int32_t *__restrict__ pop_start, int n_pops,
                                                   const int32_t *__restrict__ order, int min_pair_sites, int diag_nan,

@@ -826,6 +826,56 @@ class WindowBatch:
                 out[lay.ind_order[t]][lay.ind_order[s]] = v
         return out
 
+    # -- nearest reference population (distPaint.py) -------------------------------------------------------
+    def paint(self, ref_lists, minSites, p_threshold=0.05, delta_threshold=None, noresult=-1):
+        """distPaint.py:62-87 for every window: int32 [n_win][n_ind], the reference population (index into ref_lists) every individual
+        is nearest to, or noresult.  Individuals are the rows of the reference's alignment (every sample haploid; names sorted,
+        lay.ref_order): column k is the k-th of them and ref_lists[p] holds population p's reference individuals as such indices, in
+        the reference's order, duplicates kept.  delta_threshold None: the rank-sum test against p_threshold (the device compares
+        integer rank sums with paint_crit's table); else the two lowest means must lie delta_threshold apart, and the cells with a
+        nan among their means come back with those means and are finished here with Python's sorted(), as the reference does it
+        (self.paint_host_cells: which cells those were).  Every window is decided, whatever its number of sites: a driver leaves
+        out the windows below its minSites."""
+        lay = self.lay
+        assert lay.n_hap == lay.n_samp, "paint: every sample must be haploid (distPaint.py reads its file that way)"
+        n_ind = lay.n_hap
+        lists = [np.asarray(r, dtype=np.int64).ravel() for r in ref_lists]
+        assert len(lists) >= 1 and all(len(r) >= 1 for r in lists), "paint: every reference population needs an individual"
+        assert all(r.min() >= 0 and r.max() < n_ind for r in lists), "paint: reference index outside the individuals"
+        delta = delta_threshold is not None
+        assert not delta or len(lists) >= 2, "paint: the delta mode needs two populations"
+        order = np.ascontiguousarray(lay.ref_order, dtype=np.int32)
+        start = np.zeros(len(lists) + 1, dtype=np.int32)
+        start[1:] = np.cumsum([len(r) for r in lists])
+        slots = np.ascontiguousarray(order[np.concatenate(lists)], dtype=np.int32)
+        out = np.zeros((self.n, n_ind), dtype=np.int32)
+        self.paint_host_cells = np.zeros((self.n, n_ind), dtype=bool)
+        if self.n == 0:
+            return out
+        crit = None if delta else paint_crit([len(r) for r in lists], p_threshold)
+        cells = self.n * n_ind
+        n_flag = C.c_int64(0)
+        fcell = np.empty(cells if delta else 1, dtype=np.int64)                 # (touched only as far as cells come back)
+        fmean = np.empty((cells if delta else 1, len(lists)), dtype=np.float64)
+        check(self.e._L.pg_paint(self.e._h, self.lo, self.hi, self.n, n_ind, order, len(lists), start, slots, int(minSites), 1 if delta else 0,
+                                 C.c_void_p(crit.ctypes.data) if crit is not None else None, float(delta_threshold) if delta else 0.0,
+                                 int(noresult), out, C.byref(n_flag), C.c_void_p(fcell.ctypes.data), C.c_void_p(fmean.ctypes.data)))
+        nf = int(n_flag.value)
+        if nf:
+            # every such cell has a nan mean: np.argmin is its first nan; sorted() compares floats as it compares np.float64.  One
+            # sorted() of a short list of Python floats per cell (about half a microsecond each: a batch with most of 10^6 cells
+            # flagged -- minSites near the pairs' shared sites -- spends a second here)
+            first_nan = np.argmax(np.isnan(fmean[:nf]), axis=1)
+            keep = np.empty(nf, dtype=bool)
+            d = float(delta_threshold)
+            for k, means in enumerate(fmean[:nf].tolist()):
+                s = sorted(means)
+                keep[k] = not s[1] - s[0] < d
+            flat = out.reshape(-1)
+            flat[fcell[:nf]] = np.where(keep, first_nan, noresult)
+            self.paint_host_cells.reshape(-1)[fcell[:nf]] = True
+        return out
+
     # -- ABBA-BABA ----------------------------------------------------------------------------------------
     def ABBABABA(self, P1, P2, P3, P4, minData):
         names = self.lay.sampleData.popNames
@@ -862,6 +912,42 @@ class WindowBatch:
                    "fdh2": f4c * 1. / sums[:, 10], "fh": f4c * 1. / sums[:, 11],
                    "ABBA": sums[:, 4], "BABA": sums[:, 5], "ABAA": sums[:, 12], "BAAA": sums[:, 13], "sitesUsed": used}
         return out                       # windows with sitesUsed == 0 carry 0.0 / nan; the drivers never print them
+
+
+def ranksum_less_p(n1, n2, twice_s):
+    """p-value of scipy.stats.ranksums(x, y, alternative="less") for len(x) = n1, len(y) = n2 and the rank sum s = twice_s / 2 of x
+    (average ranks, no tie correction): Phi((s - n1 (n1 + n2 + 1) / 2) / sqrt(n1 n2 (n1 + n2 + 1) / 12)), Phi through math.erfc"""
+    import math
+    z = (twice_s / 2.0 - n1 * (n1 + n2 + 1) / 2.0) / math.sqrt(n1 * n2 * (n1 + n2 + 1) / 12.0)
+    return 0.5 * math.erfc(-z / math.sqrt(2.0))
+
+
+def paint_crit(sizes, p_threshold):
+    """int64 [P][P] for reference populations of these sizes: crit[b][q] = the largest doubled rank sum 2 s of b's values among b's and
+    q's at which distPaint.py still assigns b (p-value <= p_threshold: `pvalue > p_threshold` is what rejects), -1 when no rank sum
+    does.  2 s runs from n1 (n1 + 1) (b's values all below q's) to n1 (n1 + 2 n2 + 1); the p-value does not fall as s grows."""
+    P = len(sizes)
+    crit = np.full((P, P), -1, dtype=np.int64)
+    known = {}
+    for b in range(P):
+        for q in range(P):
+            if b == q:
+                continue
+            n1, n2 = int(sizes[b]), int(sizes[q])
+            if (n1, n2) not in known:
+                lo, hi = n1 * (n1 + 1), n1 * (n1 + 2 * n2 + 1)
+                if not ranksum_less_p(n1, n2, lo) <= p_threshold:               # (a nan threshold assigns everything: nan > t is false)
+                    known[(n1, n2)] = hi if p_threshold != p_threshold else -1
+                else:
+                    while lo < hi:                                              # the last 2 s with p <= threshold
+                        mid = (lo + hi + 1) // 2
+                        if ranksum_less_p(n1, n2, mid) <= p_threshold:
+                            lo = mid
+                        else:
+                            hi = mid - 1
+                    known[(n1, n2)] = lo
+            crit[b, q] = known[(n1, n2)]
+    return crit
 
 
 def pop_row_order(lay):

@@ -52,7 +52,9 @@ enum pg_geno_format { PG_FMT_PHASED = 0, PG_FMT_PAIRS = 1, PG_FMT_HAPLO = 2, PG_
 enum pg_kernel_id { PG_K_PACK = 0, PG_K_PAIRWISE = 1 /* the called-count kernel (k_pairC*) */, PG_K_POPDIST_FIN = 2,
                     PG_K_SITESTATS = 3, PG_K_SYNTH = 4, PG_K_PAIRD = 5 /* the difference-count kernel (k_pairD*) */,
                     PG_K_INDPAIR_FIN = 6, PG_K_RESULT_D2H = 7 /* copy of a large result table back to the host (indPair means) */,
-                    PG_K_ORDERED = 8 /* k_popfreq_ordered: thetaPi as the reference's site-by-site sum */, PG_K_COUNT_ = 9 };
+                    PG_K_ORDERED = 8 /* k_popfreq_ordered: thetaPi as the reference's site-by-site sum */,
+                    PG_K_PAINT = 9 /* k_paint: distPaint.py's decision */, PG_K_PAINT_CALLED = 10 /* k_hap_called as pg_paint runs it: the
+                    individuals' own called counts */, PG_K_COUNT_ = 11 };
 
 int pg_abi_version(void);
 const char *pg_last_error(void);
@@ -553,6 +555,23 @@ int pg_sfs_end(pg_ctx *ctx);
 int pg_sfs_target_base(const int64_t *tot4, const int64_t *out4, int *base_out);
 /* k_site_counts alone over resident rows, HIP-event time without the copy to the host (tools/sfs_bench.py's yardstick). */
 int pg_sfs_time_site_counts(pg_ctx *ctx, int64_t site_lo, int64_t site_hi, double *ms_out);
+
+/* ---- nearest reference population per window and individual (distPaint.py) ---------------------------- */
+/* Replaces the worker loop of distPaint.py:62-87 (which_lowest_test / which_lowest_delta, distPaint.py:26-44; Alignment.pairDist and
+ * nanMask, genomics.py:903-905): the windows go through the pack and pair kernels, k_paint reads D and C in place.
+ * Every sample must be haploid (PG_ERR_STATE otherwise).  ind_slot[n_ind]: the slot behind output column k.  Reference populations as a CSR list: ref_start[n_pops + 1], ref_slot[] the
+ * slots of the reference individuals in the reference's order, duplicates kept (at most 64 populations and 2048 entries).  The distance
+ * of a pair is D / C, nan where C < min_sites or C == 0; C of an individual with itself is its own called count.
+ * mode 0 (rank-sum test): crit[n_pops][n_pops], crit[b][q] = the largest doubled rank sum 2 s of population b's values among those of b
+ * and q whose p-value (scipy.stats.ranksums, alternative "less") is <= the threshold, -1 when there is none: decision = noresult as soon
+ * as one comparison lies above it, else np.argmin of the populations' np.nanmean; a comparison with a nan on either side never rejects.
+ * mode 1 (delta): noresult where the two smallest means are closer than delta.  Cells with a nan among their means are the caller's
+ * (Python's sorted() of such a list depends on its order): *n_flagged_out of them, flag_cell_out[] = window * n_ind + column and
+ * flag_means_out[][n_pops] their means, in no particular order; both arrays need room for n_win * n_ind cells.
+ * decision_out[n_win][n_ind].  Kernel families PG_K_PAINT and PG_K_PAINT_CALLED. */
+int pg_paint(pg_ctx *ctx, const int64_t *win_lo, const int64_t *win_hi, int n_win, int n_ind, const int32_t *ind_slot, int n_pops,
+             const int32_t *ref_start, const int32_t *ref_slot, int min_sites, int mode, const int64_t *crit, double delta, int noresult,
+             int32_t *decision_out, int64_t *n_flagged_out, int64_t *flag_cell_out, double *flag_means_out);
 
 /* ---- per-haplotype called-site counts ------------------------------------------------------------ */
 /* Replaces Alignment.seqNonNan (genomics.py:1038-1040) as used by distMat.py:40 (--minPerInd):
