@@ -20,6 +20,7 @@
 //   k_bgzf_assemble  gzip header + BC field, the deflated bytes, CRC-32 and size of every member, one behind the other
 // Its output is any inflater's input (tests: zlib, k_inflate); it does not try to be zlib's bytes.
 #include "pg_ctx.h"
+#include "pg_wave.h"
 
 #include <algorithm>
 #include <vector>
@@ -85,8 +86,6 @@ struct DfShared {
 
 __device__ inline uint64_t ld64(const uint8_t *p) { uint64_t v; __builtin_memcpy(&v, p, 8); return v; }
 __device__ inline uint32_t ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ inline uint32_t rl(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-__device__ inline uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 // length 3 .. 257 -> (index of its length symbol, number of extra bits, their value); distance likewise
 __device__ inline void len_code(uint32_t len, uint32_t *idx, uint32_t *eb, uint32_t *ev) {
@@ -279,14 +278,6 @@ __device__ uint32_t df_codes_and_header(DfShared &sh, unsigned long long *total_
     return hdr_bits;
 }
 
-__device__ inline int wave_incl_scan_u(int x, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
 // in[0 .. n) -> one raw deflate stream (final block) at out (DF_SLOT bytes); returns its length (every lane)
 __device__ uint32_t df_member(const uint8_t *__restrict__ in, uint32_t n, uint8_t *__restrict__ out, uint32_t *__restrict__ tok, DfShared &sh, int lane) {
     auto stored = [&]() -> uint32_t {
@@ -394,7 +385,7 @@ __device__ uint32_t df_member(const uint8_t *__restrict__ in, uint32_t n, uint8_
         // ---- the window's tokens, from its first uncovered position ----
         while (pos < wend) {
             const int l = (int)(pos - w0);
-            const uint32_t L = rl(bestL, l);
+            const uint32_t L = pg_rl(bestL, l);
             if (L < 4) {
                 const unsigned long long mm = __builtin_amdgcn_ballot_w64(bestL >= 4) >> l;
                 uint32_t run = mm ? (uint32_t)(__ffsll((long long)mm) - 1) : 64u;
@@ -408,17 +399,17 @@ __device__ uint32_t df_member(const uint8_t *__restrict__ in, uint32_t n, uint8_
                 pos += run;
             } else {
                 uint32_t mL = L;
-                const uint32_t caps = rl(capmask, l);
+                const uint32_t caps = pg_rl(capmask, l);
                 if (!caps) {
                     if (lane == 0) {
-                        tok[nt] = rl(tokw, l);
-                        atomicAdd(&sh.freq_ll[257 + rl(lsym, l)], 1u);
-                        atomicAdd(&sh.freq_d[rl(dsym, l)], 1u);
+                        tok[nt] = pg_rl(tokw, l);
+                        atomicAdd(&sh.freq_ll[257 + pg_rl(lsym, l)], 1u);
+                        atomicAdd(&sh.freq_d[pg_rl(dsym, l)], 1u);
                     }
                 } else {
                     // the candidates that matched all sixteen bytes: the whole wave compares 256 bytes of each
-                    uint32_t mD = rl(bestD, l);
-                    const uint32_t lim = rl(maxl, l);
+                    uint32_t mD = pg_rl(bestD, l);
+                    const uint32_t lim = pg_rl(maxl, l);
                     const bool cmp = 4u * (uint32_t)lane < lim;    // (nothing is read behind the member's last dword)
                     uint32_t mine = 0;
                     if (cmp) mine = ld32(in + pos + 4u * (uint32_t)lane);
@@ -428,7 +419,7 @@ __device__ uint32_t df_member(const uint8_t *__restrict__ in, uint32_t n, uint8_
                         uint32_t q1 = 0;
 #pragma unroll
                         for (int k = 0; k < DF_NC; ++k)
-                            if (k == c) q1 = rl(q1s[k], l);
+                            if (k == c) q1 = pg_rl(q1s[k], l);
                         const uint32_t q = q1 - 1, d = pos - q;
                         uint32_t x = 1;
                         if (cmp) x = ld32(in + q + 4u * (uint32_t)lane) ^ mine;
@@ -436,7 +427,7 @@ __device__ uint32_t df_member(const uint8_t *__restrict__ in, uint32_t n, uint8_
                         uint32_t len = 256;
                         if (ne) {
                             const int k0 = __ffsll((long long)ne) - 1;
-                            len = 4u * (uint32_t)k0 + ((uint32_t)(__ffs((int)rl(x, k0)) - 1) >> 3);
+                            len = 4u * (uint32_t)k0 + ((uint32_t)(__ffs((int)pg_rl(x, k0)) - 1) >> 3);
                         }
                         if (len > lim) len = lim;
                         if (len > mL || (len == mL && d < mD)) { mL = len; mD = d; }
@@ -483,8 +474,8 @@ __device__ uint32_t df_member(const uint8_t *__restrict__ in, uint32_t n, uint8_
     unsigned long long total_bits = 0;
     uint32_t hdr_bits = 0;
     if (lane == 0) hdr_bits = df_codes_and_header(sh, &total_bits);
-    hdr_bits = rfl(hdr_bits);
-    const uint32_t tb_lo = rfl((uint32_t)total_bits), tb_hi = rfl((uint32_t)(total_bits >> 32));
+    hdr_bits = pg_rfl(hdr_bits);
+    const uint32_t tb_lo = pg_rfl((uint32_t)total_bits), tb_hi = pg_rfl((uint32_t)(total_bits >> 32));
     total_bits = ((unsigned long long)tb_hi << 32) | tb_lo;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if ((total_bits + 7) / 8 >= (unsigned long long)n + 5) return stored();
@@ -521,7 +512,7 @@ __device__ uint32_t df_member(const uint8_t *__restrict__ in, uint32_t n, uint8_
                 nb += (int)deb;
             }
         }
-        const int incl = wave_incl_scan_u(nb, lane);
+        const int incl = pg_wave_incl_scan(nb, lane);
         const uint32_t total = (uint32_t)__shfl(incl, 63, 64);
         if (nb) {
             const uint32_t rel = obit + (uint32_t)(incl - nb) - wbase * 32u;
@@ -584,7 +575,7 @@ __global__ __launch_bounds__(64) void k_bgzf_assemble(const long long *__restric
     for (long long m = blockIdx.x; m < n_members; m += gridDim.x) {
         long long at = 0;
         for (long long k = lane; k < m; k += 64) at += (long long)out_len[k] + 26;
-        for (int d = 32; d >= 1; d >>= 1) at += __shfl_xor(at, d, 64);
+        at = pg_wave_sum(at);
         const uint32_t n = out_len[m], size = n + 26;
         const long long left = total - m * DF_PIECE;
         const uint32_t isize = (uint32_t)(left < DF_PIECE ? left : DF_PIECE);

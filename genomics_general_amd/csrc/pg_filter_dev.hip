@@ -13,6 +13,7 @@
 // regular spelling, or one on which the reference raises, hands the BLOCK to the host route (pg_filter_dev_collect reports the line).
 #include "pg_ctx.h"
 #include "pg_filter_core.h"
+#include "pg_wave.h"
 
 #include <algorithm>
 #include <cstring>
@@ -29,9 +30,6 @@ void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, i
 
 namespace {
 
-#define PGF_ST_HOST 1ll
-#define PGF_ST_OVERFLOW 2ll
-
 // per-line flags of k_filt_lines<0>
 #define PGF_L_KEPT 1        // not skipped by --include / --exclude
 #define PGF_L_PASS 2        // siteTest passes (or --noTest)
@@ -39,25 +37,6 @@ namespace {
 #define PGF_L_ROW_ERR 8     // rendering the row raises
 
 #define PGF_MAX_CELL_IN 40  // cell bytes the device takes (PGF_MAXA alleles phased: 31)
-
-__device__ inline void raise_host(long long *status, long long line) {
-    atomicOr(reinterpret_cast<unsigned long long *>(status), (unsigned long long)PGF_ST_HOST);
-    atomicMin(status + 1, line);
-}
-
-__device__ inline int32_t wave_sum(int32_t x) {
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-
-__device__ inline int wave_excl_scan(int x, int lane) {
-    int y = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(y, d, 64);
-        if (lane >= d) y += t;
-    }
-    return y - x;
-}
 
 struct FiltArgs {
     const uint8_t *text;
@@ -113,10 +92,10 @@ __device__ bool line_sums(const FiltArgs &A, const PgfConfig &cfg, const uint8_t
     }
     __syncthreads();
     if (__ballot(bad)) return false;
-    for (int b = 0; b < 4; ++b) tot->c[b] = wave_sum(t.c[b]);
-    tot->calls = wave_sum(t.calls);
-    tot->hets = wave_sum(t.hets);
-    tot->not_nn = wave_sum(t.not_nn);
+    for (int b = 0; b < 4; ++b) tot->c[b] = pg_wave_sum(t.c[b]);
+    tot->calls = pg_wave_sum(t.calls);
+    tot->hets = pg_wave_sum(t.hets);
+    tot->not_nn = pg_wave_sum(t.not_nn);
     return true;
 }
 
@@ -159,12 +138,12 @@ __global__ __launch_bounds__(64) void k_filt_lines(FiltArgs A, PgfConfig cfg) {
     const int64_t ls = i ? A.nl[i - 1] + 1 : 0, le = A.nl[i];
     const uint8_t *line = A.text + ls;
     if (le - ls > 0x7fffffffll) {
-        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; raise_host(A.status, i); }
+        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; pg_raise_host(A.status, i); }
         return;
     }
     const uint32_t n = (uint32_t)(le - ls);
     if (!line_tabs(line, n, cfg.n_cols, lane, tabs)) {
-        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; raise_host(A.status, i); }
+        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; pg_raise_host(A.status, i); }
         return;
     }
     const uint32_t f0e = tabs[0], f1s = tabs[0] + 1, f1e = cfg.n_cols > 2 ? tabs[1] : n;
@@ -187,7 +166,7 @@ __global__ __launch_bounds__(64) void k_filt_lines(FiltArgs A, PgfConfig cfg) {
     PgfCounts tot;
     PgfCounts *pop = reinterpret_cast<PgfCounts *>(tabs + cfg.n_cols);
     if (!line_sums(A, cfg, line, tabs, n, lane, &tot, pop)) {       // (a cell the reference raises on is worded by the host)
-        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; raise_host(A.status, i); }
+        if (!RENDER && lane == 0) { A.flags[i] = 0; A.rlen[i] = 0; pg_raise_host(A.status, i); }
         return;
     }
     int order[4];
@@ -217,7 +196,7 @@ __global__ __launch_bounds__(64) void k_filt_lines(FiltArgs A, PgfConfig cfg) {
                 if (L < 0) err = true;
                 else sum += L + 1;
             }
-            sum = wave_sum(sum);
+            sum = pg_wave_sum(sum);
             if (__ballot(err)) fl |= PGF_L_ROW_ERR;
             else len = f1e + (uint32_t)sum + 1;
         }
@@ -226,7 +205,7 @@ __global__ __launch_bounds__(64) void k_filt_lines(FiltArgs A, PgfConfig cfg) {
         if (lane == 0) {
             A.flags[i] = fl;
             A.rlen[i] = (fl & PGF_L_ROW_ERR) ? 0 : len;
-            if (host) raise_host(A.status, i);
+            if (host) pg_raise_host(A.status, i);
         }
         return;
     }
@@ -247,7 +226,7 @@ __global__ __launch_bounds__(64) void k_filt_lines(FiltArgs A, PgfConfig cfg) {
             if (L < 0) L = 0;                                      // (cannot happen: k_filt_lines<0> sent such rows to the host)
         }
         const int w = j < cfg.n_sel ? L + 1 : 0;
-        const int off = wave_excl_scan(w, lane);
+        const int off = pg_wave_excl_scan(w, lane);
         if (j < cfg.n_sel) {
             uint8_t *d = o + at + (uint32_t)off;
             d[0] = '\t';
@@ -276,9 +255,9 @@ __global__ __launch_bounds__(64) void k_filt_thin(FiltArgs A, PgfConfig cfg) {
         for (int64_t k = 0; same && k < cn; ++k) same = A.text[ls + k] == A.text[last_s + k];
         if (!same) { last_s = ls; last_n = cn; have = true; }
         const bool keep = pgf_thin_keep(same, A.pos[i], &last_pos, cfg.thin_dist);
-        if (keep && (fl & PGF_L_TEST_ERR)) { raise_host(A.status, i); return; }
+        if (keep && (fl & PGF_L_TEST_ERR)) { pg_raise_host(A.status, i); return; }
         const bool pass = keep && (fl & PGF_L_PASS);
-        if (pass && (fl & PGF_L_ROW_ERR)) { raise_host(A.status, i); return; }
+        if (pass && (fl & PGF_L_ROW_ERR)) { pg_raise_host(A.status, i); return; }
         if (pass) last_pos = A.pos[i];
         else A.rlen[i] = 0;
     }
@@ -447,7 +426,7 @@ extern "C" int pg_filter_dev_parse(pg_ctx *c, int slot) {
     }
     // a block without a final line feed (the file's partial last line) is the host's; a '\r' in a line sends it there too (k_filt_lines)
     const bool host_now = F.no_final_newline || n_lines == 0;
-    F.h_status.p[0] = host_now ? PGF_ST_HOST : 0;
+    F.h_status.p[0] = host_now ? PG_ST_HOST : 0;
     F.h_status.p[1] = host_now ? 0 : 0x7fffffffffffffffll;
     F.h_status.p[2] = F.h_status.p[3] = F.h_status.p[4] = 0;
     if (host_now) {
@@ -496,7 +475,7 @@ extern "C" int pg_filter_dev_collect(pg_ctx *c, int slot, int64_t *rows_len_out,
     F.state = 0;
     if (n_lines_out) *n_lines_out = F.n_lines;
     if ((rc = pg_tok_crc_result(c, slot)) != PG_OK) return rc;
-    if (F.h_status.p[0] == PGF_ST_OVERFLOW) {                     // only the rows' room: grow it, render again
+    if (F.h_status.p[0] == PG_ST_OVERFLOW) {                     // only the rows' room: grow it, render again
         hipStream_t st = c->stream_up;
         if ((rc = F.out.ensure_roomy((size_t)F.h_status.p[2] + 4096 + 64)) != PG_OK) return rc;
         F.out_cap = (int64_t)F.out.cap - 64;
@@ -507,7 +486,7 @@ extern "C" int pg_filter_dev_collect(pg_ctx *c, int slot, int64_t *rows_len_out,
         HIPCHK(hipEventSynchronize(F.done));
     }
     if (F.h_status.p[0]) {
-        *host_line_out = (F.h_status.p[0] & PGF_ST_HOST) ? F.h_status.p[1] : 0;
+        *host_line_out = (F.h_status.p[0] & PG_ST_HOST) ? F.h_status.p[1] : 0;
         ++c->filt.host_blocks;
         return PG_OK;
     }

@@ -7,6 +7,7 @@
 //   pg_inflate_device        members -> text on the device, result copied back (tests, tools/inflate_bench.py)
 //   pg_tokenize_submit_bgzf  the submit step of the device tokenizer for a block that is still deflated
 #include "pg_ctx.h"
+#include "pg_wave.h"
 #include "pg_inflate_core.h"
 #include "pg_fast_inflate.h"
 #include "pg_par_gunzip.h"
@@ -141,8 +142,7 @@ __device__ inline uint32_t crc_wave(const uint8_t *__restrict__ p, uint32_t n, c
         }
         s = crc_mul(tab[1280 + (N - j)], s ^ w[j]);                      // N - j in 1 .. 64 dwords to the end of the aligned part
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s ^= (uint32_t)__shfl_xor((int)s, d, 64);
+    s = pg_wave_xor(s);
     if (lane == 0) {
         const uint8_t *q = p + head + 4u * N;
         for (uint32_t k = 0; k < t; ++k) s = tab[(s ^ q[k]) & 255u] ^ (s >> 8);

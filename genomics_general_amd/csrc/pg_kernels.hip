@@ -13,6 +13,7 @@
 // same IEEE operations, in the same order, as the NumPy expressions of the reference.
 #include "pg_internal.h"
 #include "pg_range_counts.h"
+#include "pg_wave.h"
 #include <algorithm>
 #ifdef PG_DIV_PROBE
 #include <cstdio>
@@ -114,10 +115,7 @@ __device__ __forceinline__ double block_sum_f64(double v, double *sh) {
 template <int N>
 __device__ __forceinline__ void block_sum_multi(double (&v)[N], double *sh /* [waves][N] */) {
 #pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v[k] += __shfl_xor(v[k], m, 64);
-    }
+    for (int k = 0; k < N; ++k) v[k] = pg_wave_sum(v[k]);
     const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -781,8 +779,7 @@ __global__ __launch_bounds__(256) void k_popdist_np(const int32_t *__restrict__ 
         __syncthreads();
     }
     // the valid elements of the block (an integer, any order)
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) valid += __shfl_xor(valid, m, 64);
+    valid = pg_wave_sum(valid);
     if ((tid & 63) == 0) shc[tid >> 6] = valid;
     __syncthreads();
     if (tid == 0) {
@@ -1399,8 +1396,7 @@ __global__ __launch_bounds__(64) void k_quartet_np(const int8_t *__restrict__ gt
         masked(q0 + lane, bits);
         n += __popc(bits[0]) + __popc(bits[1]) + __popc(bits[2]) + __popc(bits[3]);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m, 64);
+    n = pg_wave_sum(n);
     // the stream of used sites: list[list_pos .. list_len) of the step that starts at flag group q_next - 64
     int64_t q_next = q_first, step_site0 = 0;
     int list_len = 0, list_pos = 0;
@@ -1409,12 +1405,7 @@ __global__ __launch_bounds__(64) void k_quartet_np(const int8_t *__restrict__ gt
             uint32_t bits[4];
             masked(q_next + lane, bits);
             const int cnt = __popc(bits[0]) + __popc(bits[1]) + __popc(bits[2]) + __popc(bits[3]);
-            int pre = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int v = __shfl_up(pre, d, 64);
-                if (lane >= d) pre += v;
-            }
+            const int pre = pg_wave_incl_scan(cnt, lane);
             const int total = __shfl(pre, 63, 64);
             int k = pre - cnt;
             __syncthreads();                                             // the previous step's list has been consumed
@@ -1815,12 +1806,7 @@ __global__ __launch_bounds__(64) void k_popfreq_ordered(const int8_t *__restrict
             }
             const int cnt = __popc(bits[0]) + __popc(bits[1]) + __popc(bits[2]) + __popc(bits[3]);
             if (__ballot(cnt != 0) == 0ull) continue;                        // (wave-uniform) nothing flagged among these 8192 sites
-            int pre = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int v = __shfl_up(pre, d, 64);
-                if (lane >= d) pre += v;
-            }
+            const int pre = pg_wave_incl_scan(cnt, lane);
             const int total = __shfl(pre, 63, 64);
             int k = pre - cnt;
 #pragma unroll

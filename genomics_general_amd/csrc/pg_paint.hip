@@ -18,6 +18,7 @@
 //        sorted() of such a list depends on its order, so the cell is appended to a list (cell index, its means) and the host
 //        finishes it with sorted() itself.
 #include "pg_ctx.h"
+#include "pg_wave.h"
 
 #include <algorithm>
 #include <vector>
@@ -117,8 +118,7 @@ __global__ __launch_bounds__(64 * PAINT_WAVES) void k_paint(const int32_t *__res
                 }
                 twice_s += 1 + 2 * (long long)less + eq;
             }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) twice_s += __shfl_xor(twice_s, m, 64);
+            twice_s = pg_wave_sum(twice_s);
             if (twice_s > limit) {                                // (limit -1: no rank sum of these sizes reaches the threshold)
                 result = noresult;
                 break;

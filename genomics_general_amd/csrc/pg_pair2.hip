@@ -28,6 +28,7 @@
 //                                          partial word); p = 0: x, p = 1: v; the planes of a haplotype are adjacent (rows: two
 //                                          s_load_dwordx16 per 16 haplotypes, column: one 8-byte load); two padding words at the end
 #include "pg_internal.h"
+#include "pg_pair_common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -711,16 +712,10 @@ __device__ __forceinline__ void emit_poly_sites(const uint32_t pr[4], const uint
 constexpr int PACK_FUSE_XC = 2;                      // XV words a wave holds back in LDS (4 uint4 cells per lane and word)
 constexpr int PACK_FUSE_NB = 3;                      // iterations of cells in LDS: a wave may run up to two iterations ahead of the slowest
 constexpr int PACK_FUSE_SPINS = 1 << 22;             // polls of an LDS counter before a wave gives up (PG_FLAG_FUSE_STALL)
-typedef int fz_v8i __attribute__((ext_vector_type(8)));
-typedef float fz_v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ fz_v16f fz_mfma(const fz_v8i &a, const fz_v8i &b, const fz_v16f &c) {       // both operands e2m1, scales 2^0
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 0, 0, 0);
-}
 
 // The operands of K step s of one iteration's cells fb: a wave's four tile rows (cells ia[p]) and two tile columns (ib[p]); UW =
 // cells per word.  fp4 operands are the first four registers; the others are not read.
-__device__ __forceinline__ void fuse_frags(const uint4 *fb, int s, int UW, const int ia[4], const int ib[2], fz_v8i fa_[4], fz_v8i fb_[2]) {
+__device__ __forceinline__ void fuse_frags(const uint4 *fb, int s, int UW, const int ia[4], const int ib[2], v8i fa_[4], v8i fb_[2]) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const uint4 x = fb[2 * s * UW + ia[p]];
@@ -733,24 +728,6 @@ __device__ __forceinline__ void fuse_frags(const uint4 *fb, int s, int UW, const
     }
 }
 
-// XCD-aware block -> (window, part), as the pair kernels deal their blocks (pg_pair_mfma.hip)
-__device__ __forceinline__ bool fuse_win_decode(int per_win, int n_win, int &win, int &rem) {
-    const int xcd = blockIdx.x & 7;
-    const int v = blockIdx.x >> 3;
-    const int full = n_win >> 3;
-    if (v < full * per_win) {
-        win = (v / per_win) * 8 + xcd;
-        rem = v % per_win;
-        return true;
-    }
-    const int total = (n_win & 7) * per_win, q = (total + 7) >> 3;
-    const int vt = v - full * per_win, lin = xcd * q + vt;
-    if (vt >= q || lin >= total) return false;
-    win = full * 8 + lin / per_win;
-    rem = lin % per_win;
-    return true;
-}
-
 template <int DIP>
 __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int RS, const int64_t *__restrict__ win_lo,
                                             const int64_t *__restrict__ win_hi, const int64_t *__restrict__ goff,
@@ -759,7 +736,7 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
     constexpr int VN = DIP ? 4 : 8;                      // units per lane
     extern __shared__ uint4 fz_lds[];                    // frag[NB][8][32 T] | stage_x[8 waves][PACK_FUSE_XC * 4][64 lanes] | counters
     int b, kp;
-    if (!fuse_win_decode(fa.kparts, fa.n_win, b, kp)) return;          // block-uniform
+    if (!pg_deal_window(blockIdx.x, fa.kparts, fa.n_win, b, kp)) return;          // block-uniform
     const int UW = 32 * fa.T;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint4 *const frag = fz_lds;
@@ -792,7 +769,7 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
     for (int p = 0; p < 4; ++p) ia[p] = kb * UW + 32 * (int)fa.a[wave][p] + r;
 #pragma unroll
     for (int p = 0; p < 2; ++p) ib[p] = kb * UW + 32 * (int)fa.b[wave][p] + r;
-    fz_v16f acc[4];
+    v16f acc[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -840,25 +817,25 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
         const uint4 *fb = frag + pslot * 8 * UW;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            fz_v8i fa_[4], fb_[2];
+            v8i fa_[4], fb_[2];
             fuse_frags(fb, q, UW, ia, ib, fa_, fb_);
             uint32_t re[4], rq[4];
             __builtin_amdgcn_sched_barrier(0);
             trans_even(d + 8 * q, re);
             asm volatile("" : "+v"(re[0]), "+v"(re[1]), "+v"(re[2]), "+v"(re[3]));          // (computed here, not where it is first used)
             __builtin_amdgcn_sched_barrier(0);
-            acc[0] = fz_mfma(fa_[0], fb_[0], acc[0]);
+            acc[0] = pg_mfma_fp4(fa_[0], fb_[0], acc[0]);
             __builtin_amdgcn_sched_barrier(0);
             trans_odd(d + 8 * q, rq);
             asm volatile("" : "+v"(rq[0]), "+v"(rq[1]), "+v"(rq[2]), "+v"(rq[3]));
             __builtin_amdgcn_sched_barrier(0);
-            acc[1] = fz_mfma(fa_[1], fb_[1], acc[1]);
+            acc[1] = pg_mfma_fp4(fa_[1], fb_[1], acc[1]);
             __builtin_amdgcn_sched_barrier(0);
             keep_presence(q, re, rq, R[q], pa);
             asm volatile("" : "+v"(pa[0]), "+v"(pa[1]), "+v"(pa[2]), "+v"(pa[3]));
             __builtin_amdgcn_sched_barrier(0);
-            acc[2] = fz_mfma(fa_[2], fb_[0], acc[2]);
-            acc[3] = fz_mfma(fa_[3], fb_[1], acc[3]);
+            acc[2] = pg_mfma_fp4(fa_[2], fb_[0], acc[2]);
+            acc[3] = pg_mfma_fp4(fa_[3], fb_[1], acc[3]);
             __builtin_amdgcn_sched_barrier(0);
         }
         arrive(&done[pslot]);
@@ -895,34 +872,21 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
     wait_ge(&ready[pslot], pround8 + 8);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {            // the last iteration's cells: no word left to transpose between the products
-        fz_v8i fa_[4], fb_[2];
+        v8i fa_[4], fb_[2];
         fuse_frags(frag + pslot * 8 * UW, q, UW, ia, ib, fa_, fb_);
 #pragma unroll
-        for (int p = 0; p < 4; ++p) acc[p] = fz_mfma(fa_[p], fb_[p & 1], acc[p]);
+        for (int p = 0; p < 4; ++p) acc[p] = pg_mfma_fp4(fa_[p], fb_[p & 1], acc[p]);
     }
     if (stalled && lane == 0) atomicOr(mismatch, PG_FLAG_FUSE_STALL);
     vs.finish();
     xs.flush();
     if (DIP && (bad & 0x88888888u)) atomicOr(mismatch, 1);
-    // accumulator tiles (count / 4) -> upper triangle of the window's matrix: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-    const int n = fa.n_units, atomic = fa.kparts > 1;
+    // the accumulators hold count / 4
+    const int n = fa.n_units;
     int32_t *Cw = fa.Cmat + (size_t)b * n * n;
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        if (!((fa.mask[wave] >> p) & 1)) continue;
-        const int I = fa.a[wave][p], J = fa.b[wave][p & 1];
-        const int col = 32 * J + (lane & 31);
-        if (col >= n) continue;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int row = 32 * I + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-            if (row >= n || row > col || (row == col && !fa.diag)) continue;
-            const int32_t v = (int32_t)(acc[p][reg] * 4.0f);
-            int32_t *dst = &Cw[(size_t)row * n + col];
-            if (atomic) { if (v) atomicAdd(dst, v); }
-            else *dst = v;
-        }
-    }
+    for (int p = 0; p < 4; ++p)
+        if ((fa.mask[wave] >> p) & 1) pg_store_tile<4>(acc[p], fa.a[wave][p], fa.b[wave][p & 1], lane, n, fa.diag, fa.kparts > 1, Cw);
 }
 
 // BURST: the plane stores of a thread wait in LDS cells of its own (no barrier) and leave together -- the called plane every
@@ -1156,15 +1120,14 @@ int pg_launch_pack_fused(hipStream_t st, const int8_t *gt, int RS, const int64_t
     fa.Cmat = Cmat;
     pg_fuse_tasks(fa.T, fa);
     // one block fills a CU (8 waves of up to 256 registers): a batch of few windows is cut into parts until the blocks go round
-    // the 256 CUs about four times, as long as a part keeps 64 words (8 iterations); an f32 accumulator holds count / 4 exactly
-    // while count < 2^24: parts below 2^23 sites
+    // the 256 CUs about four times, as long as a part keeps 64 words (8 iterations)
     int64_t kparts = n_win >= 1024 ? 1 : (1024 + n_win - 1) / n_win;
     kparts = std::min<int64_t>(kparts, std::max<int64_t>(1, avg_words / 64));
-    kparts = std::max<int64_t>(kparts, (max_words * 32 + (1 << 23) - 1) >> 23);
+    kparts = std::max<int64_t>(kparts, pg_exact_parts(max_words * 32));
     fa.kparts = (int)kparts;
-    if (kparts > 1) (void)hipMemsetAsync(Cmat, 0, (size_t)n_win * n_units * n_units * 4, st);
+    pg_zero_if_parts(st, Cmat, n_win, n_units, kparts);
     const size_t lds = (size_t)(PACK_FUSE_NB * 8 * 32 * fa.T + 8 * PACK_FUSE_XC * 4 * 64 + 2) * sizeof(uint4);
-    const int64_t blocks = (int64_t)((n_win + 7) / 8) * kparts * 8;
+    const int64_t blocks = pg_deal_blocks(n_win, kparts);
 #define PG_PACK3F(D)                                                                                                              \
     do {                                                                                                                          \
         static bool ready = false;                       /* more than 64 KB of dynamic LDS: asked for once per form */            \
@@ -1200,8 +1163,7 @@ void pg_launch_pack2(hipStream_t st, const int8_t *gt, int RS, const int64_t *wi
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Task decoding shared by k_pairC / k_pairD.  1-D XCD-aware grid: block b runs on XCD b % 8; all waves of a window go
-// to one XCD so its planes are served by that XCD's L2 (except the last n_win % 8 windows, which are spread over all XCDs).
+// Task decoding shared by k_pairC / k_pairD (the blocks are dealt to the windows by pg_deal_window).
 // ------------------------------------------------------------------------------------------------------
 struct PairCtx {
     int win, row0, nsub, col0, lower, lane, ks;
@@ -1212,23 +1174,8 @@ struct PairCtx {
 // kso > 1 additionally cuts the word range across blocks (more waves in flight when there are few windows x tasks); those
 // partial counts are combined with integer atomics (exact, order independent).
 __device__ __forceinline__ bool pair_decode(const PgTask2 *__restrict__ tasks, int n_tasks, int kso, int n_win, PairCtx &c) {
-    const int xcd = blockIdx.x & 7;
-    const int v = blockIdx.x >> 3;
-    const int per_win = n_tasks * kso;
-    const int full = n_win >> 3;                       // rows of 8 windows: window 8*row + xcd runs on XCD xcd
     int rem;
-    if (v < full * per_win) {
-        c.win = (v / per_win) * 8 + xcd;
-        rem = v % per_win;
-    } else {
-        // the last n_win % 8 windows (all of them when a job has fewer than 8, e.g. a whole-genome distMat): their blocks are
-        // dealt to the 8 XCDs in equal contiguous runs, so that no XCD idles and neighbouring tasks still share an L2
-        const int total = (n_win & 7) * per_win, q = (total + 7) >> 3;
-        const int vt = v - full * per_win, lin = xcd * q + vt;
-        if (vt >= q || lin >= total) return false;     // block-uniform
-        c.win = full * 8 + lin / per_win;
-        rem = lin % per_win;
-    }
+    if (!pg_deal_window(blockIdx.x, n_tasks * kso, n_win, c.win, rem)) return false;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     c.ks = (rem / n_tasks) * 4 + wave;                 // this wave's part of the 4*kso parts of the word range
     c.lane = threadIdx.x & 63;
@@ -1341,6 +1288,7 @@ __global__ __launch_bounds__(256) void k_pairC(const uint32_t *__restrict__ Vp, 
 }
 
 // extra cut of the word range across blocks: wanted when windows x tasks x 4 waves cannot fill 256 CUs x 4 SIMDs x 8
+// (not pg_pick_parts: a block is four waves that already share the range, and the cut stops at 16)
 static int pick_kso(int n_win, int n_tasks, int64_t steps_per_window, int min_steps) {
     int64_t waves = (int64_t)n_win * n_tasks * 4;
     int ks = 1;
@@ -1352,8 +1300,8 @@ void pg_launch_pairC(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, i
                      int NPv, int n_units, int diag, int64_t avg_wq, int32_t *Cmat) {
     if (n_win <= 0 || n_tasks <= 0) return;
     const int kso = pick_kso(n_win, n_tasks, avg_wq, 24);
-    if (kso > 1) (void)hipMemsetAsync(Cmat, 0, (size_t)n_win * n_units * n_units * 4, st);
-    const int64_t blocks = (int64_t)((n_win + 7) / 8) * n_tasks * kso * 8;
+    pg_zero_if_parts(st, Cmat, n_win, n_units, kso);
+    const int64_t blocks = pg_deal_blocks(n_win, (int64_t)n_tasks * kso);
     hipLaunchKernelGGL(k_pairC, dim3((unsigned)blocks), dim3(256), 0, st, Vp, vgoff, n_win, tasks, n_tasks, kso, NPv, n_units,
                        diag, Cmat);
 }
@@ -1417,8 +1365,8 @@ void pg_launch_pairD(hipStream_t st, const uint32_t *XV, const int32_t *nw, cons
                      const PgTask2 *tasks, int n_tasks, int NP, int N, int64_t avg_groups, int32_t *Dmat, int capg) {
     if (n_win <= 0 || n_tasks <= 0) return;
     const int kso = pick_kso(n_win, n_tasks, avg_groups, 1);
-    if (kso > 1) (void)hipMemsetAsync(Dmat, 0, (size_t)n_win * N * N * 4, st);
-    const int64_t blocks = (int64_t)((n_win + 7) / 8) * n_tasks * kso * 8;
+    pg_zero_if_parts(st, Dmat, n_win, N, kso);
+    const int64_t blocks = pg_deal_blocks(n_win, (int64_t)n_tasks * kso);
     hipLaunchKernelGGL(k_pairD, dim3((unsigned)blocks), dim3(256), 0, st, XV, nw, goff, n_win, tasks, n_tasks, kso, NP, N, Dmat, capg);
 }
 

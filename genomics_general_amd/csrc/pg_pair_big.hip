@@ -10,6 +10,7 @@
 // wave on a SIMD the matrix pipe is busy only while that wave's next instruction is a product whose operands are ready.
 // A block is one window part: one wave up to 10 tiles, two waves beyond (28 tiles at 200 units), the plane fetched once.
 #include "pg_internal.h"
+#include "pg_pair_common.h"
 #include "pg_pairc_big.inc"
 
 #include <algorithm>
@@ -18,40 +19,6 @@
 #include <cstring>
 
 namespace {
-
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ bool win_decode(int per_win, int n_win, int &win, int &rem) {       // as in pg_pair_tile.hip
-    const int xcd = blockIdx.x & 7;
-    const int v = blockIdx.x >> 3;
-    const int full = n_win >> 3;
-    if (v < full * per_win) {
-        win = (v / per_win) * 8 + xcd;
-        rem = v % per_win;
-        return true;
-    }
-    const int total = (n_win & 7) * per_win, q = (total + 7) >> 3;
-    const int vt = v - full * per_win, lin = xcd * q + vt;
-    if (vt >= q || lin >= total) return false;
-    win = full * 8 + lin / per_win;
-    rem = lin % per_win;
-    return true;
-}
-
-// accumulator tile (count / 4) -> upper triangle of the window's matrix (column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5))
-__device__ __forceinline__ void store_tile(const v16f &acc, int I, int J, int lane, int n, int diag, int atomic, int32_t *__restrict__ M) {
-    const int col = 32 * J + (lane & 31);
-    if (col >= n) return;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int row = 32 * I + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-        if (row >= n || row > col || (row == col && !diag)) continue;
-        const int32_t v = (int32_t)(acc[reg] * 4.0f);
-        int32_t *dst = &M[(size_t)row * n + col];
-        if (atomic) { if (v) atomicAdd(dst, v); }
-        else *dst = v;
-    }
-}
 
 template <int T> struct Tiles;
 #define PG_BIG_TILES(T_)                                                              \
@@ -80,7 +47,7 @@ void k_pairC_big(const uint32_t *__restrict__ Vp, const int64_t *__restrict__ vg
                  int diag, int32_t *__restrict__ Cmat) {
     extern __shared__ uint4 lds[];                            // ring: PG_CBIG_RING_PAIRS x T KiB
     int win, kp;
-    if (!win_decode(kparts, n_win, win, kp)) return;
+    if (!pg_deal_window(blockIdx.x, kparts, n_win, win, kp)) return;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 31, kb = lane >> 5;
     const int64_t vg = vgoff[win];
@@ -96,7 +63,7 @@ void k_pairC_big(const uint32_t *__restrict__ Vp, const int64_t *__restrict__ vg
         for (int e = 0; e < 16; ++e) acc[n][e] = 0.0f;
     if (npair > 0) {
         const uint4 *ga = reinterpret_cast<const uint4 *>(Vp) + ((size_t)vg + q0 + kb) * NPv + r;
-        const uint32_t ring = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)lds;
+        const uint32_t ring = lds_addr(lds);
         const uint32_t lrd = ring + 16u * lane;
         const int stride = 2 * NPv * 16;
         if constexpr (T == 1) PG_BIG_RUN(PG_CBIG_ASM_T1);
@@ -112,22 +79,14 @@ void k_pairC_big(const uint32_t *__restrict__ Vp, const int64_t *__restrict__ vg
 #pragma unroll
         for (int n = 0; n < 14; ++n) {
             const int i = tl[wave][n][0], j = tl[wave][n][1];
-            if (i >= 0) store_tile(acc[n], i, j, lane, n_units, diag, atomic, Cw);
+            if (i >= 0) pg_store_tile<4>(acc[n], i, j, lane, n_units, diag, atomic, Cw);          // the accumulators hold count / 4
         }
     }
 }
 
-int pick_parts(int n_win, int waves_per_win, int64_t steps_per_window, int min_steps) {
-    const int64_t waves = (int64_t)n_win * waves_per_win;
-    int kp = 1;
-    while (kp < 64 && waves * kp < 2048 && steps_per_window / (kp * 2) >= min_steps) kp *= 2;
-    return kp;
-}
-
 template <int T>
 void launch(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, int n_win, int kparts, int NPv, int n_units, int diag, int32_t *Cmat) {
-    const int64_t blocks = (int64_t)((n_win + 7) / 8) * kparts * 8;
-    hipLaunchKernelGGL((k_pairC_big<T>), dim3((unsigned)blocks), dim3(64 * Tiles<T>::W), (size_t)PG_CBIG_RING_PAIRS * T * 1024, st, Vp, vgoff,
+    hipLaunchKernelGGL((k_pairC_big<T>), dim3((unsigned)pg_deal_blocks(n_win, kparts)), dim3(64 * Tiles<T>::W), (size_t)PG_CBIG_RING_PAIRS * T * 1024, st, Vp, vgoff,
                        n_win, kparts, NPv, n_units, diag, Cmat);
 }
 
@@ -147,9 +106,8 @@ void pg_launch_pairC_big(hipStream_t st, const uint32_t *Vp, const int64_t *vgof
     if (n_win <= 0 || n_units <= 0) return;
     const int T = (n_units + 31) / 32;
     const int W = T * (T + 1) / 2 <= 14 ? 1 : 2;
-    // an f32 accumulator holds count / 4 exactly while count < 2^24: parts below 2^23 sites; more parts when the windows are few
-    const int kparts = std::max(pick_parts(n_win, W, avg_wq / 2, 32), (int)((max_sites + (1 << 23) - 1) >> 23));
-    if (kparts > 1) (void)hipMemsetAsync(Cmat, 0, (size_t)n_win * n_units * n_units * 4, st);
+    const int kparts = std::max(pg_pick_parts(n_win, W, avg_wq / 2, 32, 2048), pg_exact_parts(max_sites));
+    pg_zero_if_parts(st, Cmat, n_win, n_units, kparts);
     switch (T) {
         case 1: launch<1>(st, Vp, vgoff, n_win, kparts, NPv, n_units, diag, Cmat); break;
         case 2: launch<2>(st, Vp, vgoff, n_win, kparts, NPv, n_units, diag, Cmat); break;

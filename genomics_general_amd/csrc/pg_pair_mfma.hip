@@ -22,13 +22,12 @@
 // part of the window's words.  These kernels serve the shapes the LDS-staged block kernels of pg_pair_tile.hip do not take
 // (planes of more than ~340 units per word) and, by default, the D counts.
 #include "pg_internal.h"
+#include "pg_pair_common.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
-
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 #define PG_MFMA_WAVES 4
 constexpr int TB = 2;                  // a wave owns up to TB x TB tiles of 32 x 32: 4 x 16 accumulator registers
@@ -56,42 +55,6 @@ int task_count(int T) {
     for (int i0 = 0; i0 < T; i0 += TB) n += (T - i0 + TB - 1) / TB;
     return n;
 }
-
-// XCD-aware block -> (window, rest): block b runs on XCD b % 8; all blocks of a window go to one XCD, so the window's planes are
-// served by that XCD's L2 (the last n_win % 8 windows are dealt over all XCDs in contiguous runs).  Same dealing as pair_decode.
-__device__ __forceinline__ bool win_decode(int per_win, int n_win, int &win, int &rem) {
-    const int xcd = blockIdx.x & 7;
-    const int v = blockIdx.x >> 3;
-    const int full = n_win >> 3;
-    if (v < full * per_win) {
-        win = (v / per_win) * 8 + xcd;
-        rem = v % per_win;
-        return true;
-    }
-    const int total = (n_win & 7) * per_win, q = (total + 7) >> 3;
-    const int vt = v - full * per_win, lin = xcd * q + vt;
-    if (vt >= q || lin >= total) return false;
-    win = full * 8 + lin / per_win;
-    rem = lin % per_win;
-    return true;
-}
-
-// accumulator tile -> upper triangle of the window's matrix.  C/D layout of the 32x32 MFMA: column = lane & 31,
-// row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-__device__ __forceinline__ void store_tile(const v16i &acc, int I, int J, int lane, int n, int diag, int atomic, int32_t *__restrict__ M) {
-    const int col = 32 * J + (lane & 31);
-    if (col >= n) return;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int row = 32 * I + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-        if (row >= n || row > col || (row == col && !diag)) continue;
-        int32_t *dst = &M[(size_t)row * n + col];
-        if (atomic) { if (acc[reg]) atomicAdd(dst, acc[reg]); }
-        else *dst = acc[reg];
-    }
-}
-
-__device__ __forceinline__ uint32_t comp(const uint4 &v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
 // ---- C ----
 template <int NR, int NC, bool DG>
@@ -121,10 +84,7 @@ struct WordsD {
     }
 };
 
-// ---- MX fp4 products (v_mfma_scale_f32_32x32x64_f8f6f4, both operands e2m1, scales 2^0) -----------------------------------------
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
+// ---- fragments of the MX fp4 products (pg_mfma_fp4) ------------------------------------------------------------------------------
 __device__ __forceinline__ v8i expand4(uint32_t w) {
     v8i f;                                   // fp4 operands are the first four registers; the others are not read
     f[0] = (int)(w & 0x11111111u);
@@ -134,11 +94,9 @@ __device__ __forceinline__ v8i expand4(uint32_t w) {
     return f;
 }
 
-// Off the diagonal the two operands of a product are different fragments, and they need not be in the same form: a nibble with
-// only bit 0 / 1 / 2 set is 0.5 / 1.0 / 2.0, so the COLUMN fragment keeps bits 0, 1, 2 of every nibble where they are (three
-// ANDs; only bit 3, the sign, is shifted down: 5 operations instead of 7) and the ROW fragment puts the same sites into the same
-// places with the reciprocal values 2.0 / 1.0 / 0.5 / 2.0: every product of two set sites is 1.0, the accumulator is the count.
-// (A diagonal task multiplies a fragment with itself and stays with the form above: count / 4.)
+// Off the diagonal the two operands of a product are different fragments: the column / row forms that pg_pair_tile.hip explains
+// at its expand_col / expand_row (every product of two set sites is 1.0, the accumulator is the count), here with literal masks
+// and eight-register operands.  (A diagonal task multiplies a fragment with itself and stays with the form above: count / 4.)
 __device__ __forceinline__ v8i expand_col(uint32_t w) {
     v8i f;
     f[0] = (int)(w & 0x11111111u);
@@ -154,20 +112,6 @@ __device__ __forceinline__ v8i expand_row(uint32_t w) {
     f[2] = (int)((w >> 2) & 0x11111111u);
     f[3] = (int)((w >> 1) & 0x44444444u);
     return f;
-}
-
-// (scale operands 0, 0 select the unscaled encoding v_mfma_f32_32x32x64_f8f6f4 -- both scales 2^0 -- : one instruction word pair
-// less per product than the v_mfma_ld_scale + v_mfma pair, and no scale register to read)
-__device__ __forceinline__ v16f mfma4(const v8i &a, const v8i &b, const v16f &c) {
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 4, 4, 0, 0, 0, 0);
-}
-
-template <int UNIT4>     // UNIT4 = 1: the accumulator holds count / 4 (0.5 x 0.5 products, scales 2^0); 0: the count itself
-__device__ __forceinline__ void store_tile4(const v16f &acc, int I, int J, int lane, int n, int diag, int atomic, int32_t *__restrict__ M) {
-    v16i q;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) q[e] = UNIT4 ? (int)(acc[e] * 4.0f) : (int)acc[e];
-    store_tile(q, I, J, lane, n, diag, atomic, M);
 }
 
 // C: the two lane halves work on DIFFERENT word groups -- lanes 0..31 on group g, lanes 32..63 on group g+1 -- so that a 16-byte
@@ -187,7 +131,7 @@ __device__ __forceinline__ void pairC4_pair(const WordsC<NR, NC, DG> &w, bool li
         for (int i = 0; i < NR; ++i)
 #pragma unroll
             for (int j = 0; j < NC; ++j)
-                if (!DG || j >= i) acc[i][j] = mfma4(fr[i], fc[j], acc[i][j]);
+                if (!DG || j >= i) acc[i][j] = pg_mfma_fp4(fr[i], fc[j], acc[i][j]);
     }
 }
 
@@ -228,14 +172,14 @@ __device__ __forceinline__ void pairC4_task(const uint4 *__restrict__ base, int 
     for (int i = 0; i < NR; ++i)
 #pragma unroll
         for (int j = 0; j < NC; ++j)
-            if (!DG || j >= i) store_tile4<DG ? 1 : 0>(acc[i][j], I0 + i, J0 + j, lane, n_units, diag, atomic, Cw);
+            if (!DG || j >= i) pg_store_tile<DG ? 4 : 1>(acc[i][j], I0 + i, J0 + j, lane, n_units, diag, atomic, Cw);
 }
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PG_MFMA_WAVES, PG_MFMA_WAVES)))
 void k_pairC_fp4(const uint32_t *__restrict__ Vp, const int64_t *__restrict__ vgoff, int n_win, int T, int ntask, int kparts, int NPv,
                  int n_units, int diag, int32_t *__restrict__ Cmat) {
     int win, rem;
-    if (!win_decode(ntask * kparts, n_win, win, rem)) return;
+    if (!pg_deal_window(blockIdx.x, ntask * kparts, n_win, win, rem)) return;
     const int s = rem % ntask, kp = rem / ntask;
     int I0, J0, nr, nc;
     if (!task_decode(T, s, I0, J0, nr, nc)) return;
@@ -246,11 +190,11 @@ void k_pairC_fp4(const uint32_t *__restrict__ Vp, const int64_t *__restrict__ vg
     int32_t *Cw = Cmat + (size_t)win * n_units * n_units;
     if (q1 <= q0) {
         if (!atomic) {
-            v16i z;
+            v16f z;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) z[e] = 0;
+            for (int e = 0; e < 16; ++e) z[e] = 0.0f;
             for (int i = 0; i < nr; ++i)
-                for (int j = 0; j < nc; ++j) store_tile(z, I0 + i, J0 + j, lane, n_units, diag, 0, Cw);
+                for (int j = 0; j < nc; ++j) pg_store_tile<1>(z, I0 + i, J0 + j, lane, n_units, diag, 0, Cw);
         }
         return;
     }
@@ -294,12 +238,12 @@ __device__ __forceinline__ void pairD4_step(const WordsD<NR, NC, DG> &w, bool li
     for (int i = 0; i < NR; ++i)
 #pragma unroll
         for (int j = 0; j < NC; ++j)
-            if (!DG || j >= i) acc[i][j] = mfma4(ra[i], cb[j], acc[i][j]);
+            if (!DG || j >= i) acc[i][j] = pg_mfma_fp4(ra[i], cb[j], acc[i][j]);
 #pragma unroll
     for (int i = 0; i < NR; ++i)
 #pragma unroll
         for (int j = 0; j < NC; ++j)
-            if (!DG || j >= i) acc[i][j] = mfma4(rb[i], ca[j], acc[i][j]);
+            if (!DG || j >= i) acc[i][j] = pg_mfma_fp4(rb[i], ca[j], acc[i][j]);
 }
 
 template <int NR, int NC, bool DG>
@@ -339,14 +283,14 @@ __device__ __forceinline__ void pairD4_task(const uint2 *__restrict__ xv, int s0
     for (int i = 0; i < NR; ++i)
 #pragma unroll
         for (int j = 0; j < NC; ++j)
-            if (!DG || j >= i) store_tile4<DG ? 1 : 0>(acc[i][j], I0 + i, J0 + j, lane, N, 0, atomic, Dw);
+            if (!DG || j >= i) pg_store_tile<DG ? 4 : 1>(acc[i][j], I0 + i, J0 + j, lane, N, 0, atomic, Dw);
 }
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PG_MFMA_WAVES, PG_MFMA_WAVES)))
 void k_pairD_fp4(const uint32_t *__restrict__ XV, const int32_t *__restrict__ nw, const int64_t *__restrict__ goff, int n_win, int T,
                  int ntask, int kparts, int NP, int N, int32_t *__restrict__ Dmat, int capg) {
     int win, rem;
-    if (!win_decode(ntask * kparts, n_win, win, rem)) return;
+    if (!pg_deal_window(blockIdx.x, ntask * kparts, n_win, win, rem)) return;
     const int s = rem % ntask, kp = rem / ntask;
     int I0, J0, nr, nc;
     if (!task_decode(T, s, I0, J0, nr, nc)) return;
@@ -359,11 +303,11 @@ void k_pairD_fp4(const uint32_t *__restrict__ XV, const int32_t *__restrict__ nw
     const int lane = threadIdx.x & 63, atomic = kparts > 1;
     if (b <= a) {
         if (!atomic) {
-            v16i z;
+            v16f z;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) z[e] = 0;
+            for (int e = 0; e < 16; ++e) z[e] = 0.0f;
             for (int i = 0; i < nr; ++i)
-                for (int j = 0; j < nc; ++j) store_tile(z, I0 + i, J0 + j, lane, N, 0, 0, Dw);
+                for (int j = 0; j < nc; ++j) pg_store_tile<1>(z, I0 + i, J0 + j, lane, N, 0, 0, Dw);
         }
         return;
     }
@@ -381,33 +325,21 @@ void k_pairD_fp4(const uint32_t *__restrict__ XV, const int32_t *__restrict__ nw
 #undef PG_D_TASK
 }
 
-// extra cut of the word range across blocks: wanted when windows x segments cannot give every SIMD a few waves
-int pick_parts(int n_win, int ntask, int64_t steps_per_window, int min_steps) {
-    const int64_t waves = (int64_t)n_win * ntask;
-    int kp = 1;
-    while (kp < 64 && waves * kp < 4096 && steps_per_window / (kp * 2) >= min_steps) kp *= 2;
-    return kp;
-}
-
-// fp4 path: an f32 accumulator holds count / 4 exactly while count < 2^24; no part of any window may see more sites than that
-// (2^23 keeps a margin); the parts are combined by integer atomics
-int exact_parts(int64_t max_sites_per_window) { return (int)((max_sites_per_window + (1 << 23) - 1) >> 23); }
-
 }  // namespace
 
 void pg_launch_pairC_mfma(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, int n_win, int NPv, int n_units, int diag,
                           int64_t avg_wq, int64_t max_sites, int32_t *Cmat) {
     if (n_win <= 0 || n_units <= 0) return;
     const int T = (n_units + 31) / 32, ntask = task_count(T);
-    int kparts = std::max(pick_parts(n_win, ntask, avg_wq, 8), exact_parts(max_sites));
+    int kparts = std::max(pg_pick_parts(n_win, ntask, avg_wq, 8, 4096), pg_exact_parts(max_sites));
     // L2 locality: the tasks of a window start together and read the same words, but they drift apart (diagonal and edge tasks
     // issue fewer products per step) and an XCD runs some 50 windows at once against 4 MB of L2 -- PMC: 9.1 GB fetched per
     // north-star launch for a 2.5 GB plane.  Parts of at most 1 MiB of plane end before the drift matters (measured on the
     // north-star shape: 1.27-1.32 ms in one part, 1.16-1.18 in two or four, 1.30 in eight, 2.3 in sixteen, zeroing included)
     const int64_t plane_bytes = avg_wq * (int64_t)NPv * 16;
     kparts = std::max(kparts, (int)std::min<int64_t>(4, (plane_bytes + (1 << 20) - 1) >> 20));
-    if (kparts > 1) (void)hipMemsetAsync(Cmat, 0, (size_t)n_win * n_units * n_units * 4, st);
-    const int64_t blocks = (int64_t)((n_win + 7) / 8) * ntask * kparts * 8;
+    pg_zero_if_parts(st, Cmat, n_win, n_units, kparts);
+    const int64_t blocks = pg_deal_blocks(n_win, (int64_t)ntask * kparts);
     hipLaunchKernelGGL(k_pairC_fp4, dim3((unsigned)blocks), dim3(64), 0, st, Vp, vgoff, n_win, T, ntask, kparts, NPv, n_units, diag, Cmat);
 }
 
@@ -415,8 +347,8 @@ void pg_launch_pairD_mfma(hipStream_t st, const uint32_t *XV, const int32_t *nw,
                           int64_t avg_words, int64_t max_vsites, int32_t *Dmat, int capg) {
     if (n_win <= 0 || N <= 0) return;
     const int T = (N + 31) / 32, ntask = task_count(T);
-    const int kparts = std::max(pick_parts(n_win, ntask, avg_words, 8), exact_parts(max_vsites));
-    if (kparts > 1) (void)hipMemsetAsync(Dmat, 0, (size_t)n_win * N * N * 4, st);
-    const int64_t blocks = (int64_t)((n_win + 7) / 8) * ntask * kparts * 8;
+    const int kparts = std::max(pg_pick_parts(n_win, ntask, avg_words, 8, 4096), pg_exact_parts(max_vsites));
+    pg_zero_if_parts(st, Dmat, n_win, N, kparts);
+    const int64_t blocks = pg_deal_blocks(n_win, (int64_t)ntask * kparts);
     hipLaunchKernelGGL(k_pairD_fp4, dim3((unsigned)blocks), dim3(64), 0, st, XV, nw, goff, n_win, T, ntask, kparts, NP, N, Dmat, capg);
 }

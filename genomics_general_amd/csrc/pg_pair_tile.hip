@@ -27,6 +27,7 @@
 //
 // The lane halves of a step hold different words, both operands in the same (permuted) site order: all a dot product needs.
 #include "pg_internal.h"
+#include "pg_pair_common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -35,9 +36,6 @@
 #include <vector>
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 
 constexpr int NSTG = 3;                // ring depth (stages)
 
@@ -53,10 +51,6 @@ __device__ __forceinline__ void glds16(const uint4 *gsrc, uint32_t lds_dst) {
                  : "memory");
 }
 
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-
 // at most n vector-memory operations of this wave still in flight (n is small and block-uniform)
 __device__ __forceinline__ void wait_vm(int n) {
     switch (n) {
@@ -66,25 +60,6 @@ __device__ __forceinline__ void wait_vm(int n) {
 #undef PG_VM
         default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
     }
-}
-
-// XCD-aware block -> (window, rest): block b runs on XCD b % 8; all blocks of a window go to one XCD (the last n_win % 8 windows
-// are dealt over all XCDs in contiguous runs).  Same dealing as pg_pair_mfma.hip.
-__device__ __forceinline__ bool win_decode(int per_win, int n_win, int &win, int &rem) {
-    const int xcd = blockIdx.x & 7;
-    const int v = blockIdx.x >> 3;
-    const int full = n_win >> 3;
-    if (v < full * per_win) {
-        win = (v / per_win) * 8 + xcd;
-        rem = v % per_win;
-        return true;
-    }
-    const int total = (n_win & 7) * per_win, q = (total + 7) >> 3;
-    const int vt = v - full * per_win, lin = xcd * q + vt;
-    if (vt >= q || lin >= total) return false;
-    win = full * 8 + lin / per_win;
-    rem = lin % per_win;
-    return true;
 }
 
 // Fragments of one word (32 sites of one unit) as e2m1 nibbles, one site per nibble.  A nibble with only bit 0 / 1 / 2 set is 0.5 /
@@ -132,25 +107,6 @@ __device__ __forceinline__ v4i expand_row(uint32_t w, const Masks &K) {
 #define PG_EXP_B(d2, d3, w) "v_and_b32 " d2 ", " w ", %[k4]\n\tv_lshrrev_b32 v239, 3, " w "\n\tv_and_b32 " d3 ", v239, %[k1]\n\t"
 #define PG_MFMA(acc, a, b) "v_mfma_f32_32x32x64_f8f6f4 " acc ", " a ", " b ", " acc " cbsz:4 blgp:4\n\t"
 #define PG_SCRATCH "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
-
-__device__ __forceinline__ uint32_t comp(const uint4 &v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
-
-// accumulator tile (the counts) -> upper triangle of the window's matrix.  C/D layout of the 32 x 32 product: column = lane & 31,
-// row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-template <int SCALE = 1>
-__device__ __forceinline__ void store_tile(const v16f &acc, int I, int J, int lane, int n, int diag, int atomic, int32_t *__restrict__ M) {
-    const int col = 32 * J + (lane & 31);
-    if (col >= n) return;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int row = 32 * I + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-        if (row >= n || row > col || (row == col && !diag)) continue;
-        const int32_t v = (int32_t)(SCALE == 1 ? acc[reg] : acc[reg] * (float)SCALE);
-        int32_t *dst = &M[(size_t)row * n + col];
-        if (atomic) { if (v) atomicAdd(dst, v); }
-        else *dst = v;
-    }
-}
 
 struct Slot { int r0, j, one; };
 __device__ __forceinline__ Slot slot_of(int32_t e) { return Slot{e & 0xff, (e >> 8) & 0xff, (e >> 16) & 1}; }
@@ -207,7 +163,7 @@ void k_pairC_tile(const uint32_t *__restrict__ Vp, const int64_t *__restrict__ v
                   int n_units, int diag, const int32_t *__restrict__ prog, int nl, int32_t *__restrict__ Cmat) {
     extern __shared__ uint4 lds[];
     int win, rem;
-    if (!win_decode(nblk * kparts, n_win, win, rem)) return;
+    if (!pg_deal_window(blockIdx.x, nblk * kparts, n_win, win, rem)) return;
     const int bp = rem % nblk, kp = rem / nblk;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 31, kb = lane >> 5;
@@ -302,8 +258,8 @@ void k_pairC_tile(const uint32_t *__restrict__ Vp, const int64_t *__restrict__ v
 #pragma unroll
         for (int s = 0; s < CS; ++s) {
             if (s < ns) {
-                store_tile(acc[s][0], sr0[s], sj[s], lane, n_units, diag, atomic, Cw);
-                if (!sone[s]) store_tile(acc[s][1], sr0[s] + 1, sj[s], lane, n_units, diag, atomic, Cw);
+                pg_store_tile<1>(acc[s][0], sr0[s], sj[s], lane, n_units, diag, atomic, Cw);          // row x column fragments: the counts
+                if (!sone[s]) pg_store_tile<1>(acc[s][1], sr0[s] + 1, sj[s], lane, n_units, diag, atomic, Cw);
             }
         }
     }
@@ -437,16 +393,6 @@ int get_program(int T, int CS, int W, const int32_t **d_out, int *nblk_out) {
     return 0;
 }
 
-// extra cut of the word range across blocks: wanted when windows x blocks cannot give every SIMD a few waves
-int pick_parts(int n_win, int waves_per_win, int64_t steps_per_window, int min_steps) {
-    const int64_t waves = (int64_t)n_win * waves_per_win;
-    int kp = 1;
-    while (kp < 64 && waves * kp < 4096 && steps_per_window / (kp * 2) >= min_steps) kp *= 2;
-    return kp;
-}
-// an f32 accumulator holds a count exactly while it is < 2^24; no part of any window may see more sites than 2^23
-int exact_parts(int64_t max_sites_per_window) { return (int)((max_sites_per_window + (1 << 23) - 1) >> 23); }
-
 constexpr int CS_C = 4, W_C = 4, GP_C = 2;      // C: 4 waves x 4 slots, stage = 2 pairs of groups (512 sites)
 
 }  // namespace
@@ -471,13 +417,13 @@ int pg_launch_pairC_tile(hipStream_t st, const uint32_t *Vp, const int64_t *vgof
     const int32_t *prog;
     int nblk;
     if (get_program(T, CS_C, W_C, &prog, &nblk) != 0) return -1;
-    const int kparts = std::max(pick_parts(n_win, nblk * W_C, avg_wq / 2, 16), exact_parts(max_sites));
-    if (kparts > 1) (void)hipMemsetAsync(Cmat, 0, (size_t)n_win * n_units * n_units * 4, st);
+    const int kparts = std::max(pg_pick_parts(n_win, nblk * W_C, avg_wq / 2, 16, 4096), pg_exact_parts(max_sites));
+    pg_zero_if_parts(st, Cmat, n_win, n_units, kparts);
     // ring shape: 2 pairs of groups per stage, 2 stages (measured on the north-star shape against 2 x 3 and 4 x 2: 1.24 / 1.31 / 1.28 ms)
     constexpr int gp = 2, nst = 2;
     const int stage_u4 = 2 * gp * NPv, chunks = stage_u4 / 64, nl = (chunks + W_C - 1) / W_C;
     const size_t lds_bytes = (size_t)nst * stage_u4 * 16;
-    const int64_t blocks = (int64_t)((n_win + 7) / 8) * nblk * kparts * 8;
+    const int64_t blocks = pg_deal_blocks(n_win, (int64_t)nblk * kparts);
     hipLaunchKernelGGL((k_pairC_tile<CS_C, W_C, gp, nst>), dim3((unsigned)blocks), dim3(64 * W_C), lds_bytes, st, Vp, vgoff, n_win, T, nblk,
                        kparts, NPv, n_units, diag, prog, nl, Cmat);
     return 0;

@@ -10,6 +10,7 @@
 //   k_tok_parse                           one wave per line: lane 0 reads scaffold + position, the lanes take the cells
 //                                         c, c+64, ... -> one-hot codes written into the row at the slots of the layout
 #include "pg_ctx.h"
+#include "pg_wave.h"
 
 #include <algorithm>
 #include <atomic>
@@ -124,8 +125,6 @@ enum { TOK_IRREGULAR = 1, TOK_BAD_POS = 2, TOK_COMMENT = 4 };
 // dip[ch]: the two one-hot codes of IUPAC diploid character ch, low nibble | high nibble << 4 (genomics.py:14-15)
 struct DipTable { uint8_t v[256]; };
 
-__device__ __forceinline__ int rl(int v, int lane) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane)); }
-
 // One wave per line.  The first 64 bytes of the line (scaffold, position, start of the cells) are read one byte per lane and
 // taken apart with ballots: the ends of the two tokens are bit scans, the position is a short scalar loop over readlane.  A line
 // whose prefix does not fit the 64 bytes (or starts with blanks) goes through the byte-by-byte walk on lane 0.
@@ -162,16 +161,16 @@ __global__ __launch_bounds__(256) void k_tok_parse(const uint8_t *__restrict__ t
                     const int64_t pls = row > 1 ? nl_pos[row - 2] + 1 : 0, ple = nl_pos[row - 1];
                     const int pnv = (int)(ple - pls < 64 ? ple - pls : 64);
                     const int pch = lane < pnv ? (int)text[pls + lane] : 10;
-                    const int p0 = rl(pch, 0);
+                    const int p0 = pg_rl_any(pch, 0);
                     prev_ok = pnv > 0 && !blank((uint8_t)p0);
                     const uint64_t neq = __ballot(ch != pch) & ((1ull << p1) - 1ull);
-                    const bool ends = p1 >= pnv ? (p1 == pnv && ple - pls == p1) : blank((uint8_t)rl(pch, p1));
+                    const bool ends = p1 >= pnv ? (p1 == pnv && ple - pls == p1) : blank((uint8_t)pg_rl_any(pch, p1));
                     differs = neq != 0ull || !ends;
                 }
                 if (r2 && prev_ok) {
                     fast = true;
-                    if (rl(ch, 0) == '#') bad |= TOK_COMMENT;
-                    const int c0 = rl(ch, d0);
+                    if (pg_rl_any(ch, 0) == '#') bad |= TOK_COMMENT;
+                    const int c0 = pg_rl_any(ch, d0);
                     const bool neg = c0 == '-';
                     if (c0 == '+' || c0 == '-') ++d0;
                     const uint64_t dg = __ballot(ch >= '0' && ch <= '9');
@@ -179,7 +178,7 @@ __global__ __launch_bounds__(256) void k_tok_parse(const uint8_t *__restrict__ t
                     long long v = 0;
                     if (p2 <= d0 || p2 - d0 > 18 || (dg & range) != range) bad |= TOK_BAD_POS;      // (up to 18 digits: int64, as the host tokenizer)
                     else
-                        for (int k = d0; k < p2; ++k) v = v * 10 + (rl(ch, k) - '0');
+                        for (int k = d0; k < p2; ++k) v = v * 10 + (pg_rl_any(ch, k) - '0');
                     cells_at = ls + __builtin_ctzll(r2);
                     if (le - cells_at != (int64_t)cells_w) bad |= TOK_IRREGULAR;
                     if (lane == 0) {

@@ -16,6 +16,7 @@
 // (pg_vcf_dev_collect reports the line; pg_vcf_dev_text brings the block's text back).
 #include "pg_ctx.h"
 #include "pg_vcf_cfg.h"
+#include "pg_wave.h"
 
 #include <algorithm>
 #include <chrono>
@@ -34,14 +35,6 @@ int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_
 
 namespace {
 
-#define PGV_ST_HOST 1ll
-#define PGV_ST_OVERFLOW 2ll
-
-__device__ inline void raise_host(long long *status, long long line) {
-    atomicOr(reinterpret_cast<unsigned long long *>(status), (unsigned long long)PGV_ST_HOST);
-    atomicMin(status + 1, line);
-}
-
 __global__ __launch_bounds__(256) void k_vcf_heads(const uint8_t *__restrict__ text, const int64_t *__restrict__ nl, int64_t n_lines,
                                                    PgvConfig cfg, const uint8_t *__restrict__ contigs, PgvLine *__restrict__ lines,
                                                    uint32_t *__restrict__ rlen, long long *__restrict__ status, const PgvKey *__restrict__ prev) {
@@ -52,11 +45,11 @@ __global__ __launch_bounds__(256) void k_vcf_heads(const uint8_t *__restrict__ t
     uint32_t bytes = 0;
     if ((uint64_t)(le - ls) > 0xfffffff0ull) {
         L->flags = 0;
-        raise_host(status, i);
+        pg_raise_host(status, i);
     } else {
         if (pgv_head(text + ls, (uint32_t)(le - ls), cfg, contigs, L) != PGV_OK) {
             L->flags = 0;
-            raise_host(status, i);
+            pg_raise_host(status, i);
         }
         if ((L->flags & PGV_LINE_KEPT) && (cfg.flags & PGV_EXCLUDE_DUPLICATES)) {
             // --excludeDuplicates: against the data line before this one -- the lines above it in the block, then the key the blocks
@@ -70,7 +63,7 @@ __global__ __launch_bounds__(256) void k_vcf_heads(const uint8_t *__restrict__ t
                 return true;
             });
             if (dup) L->flags = 0;
-            if (dup == 2) raise_host(status, i);
+            if (dup == 2) pg_raise_host(status, i);
         }
         if ((L->flags & PGV_LINE_KEPT) && !(L->flags & PGV_LINE_COMPLEX)) bytes = L->fixed_len + (uint32_t)cfg.plain_cells;
     }
@@ -92,7 +85,7 @@ __global__ void k_vcf_lastkey(const uint8_t *__restrict__ text, const int64_t *_
         if (r == 1) continue;
         if (r == 2 || cl > PGV_KEY_MAX || pl > PGV_KEY_MAX) {
             key->chrom_len = PGV_KEY_UNKNOWN;
-            raise_host(status, i);
+            pg_raise_host(status, i);
             return;
         }
         key->chrom_len = cl;
@@ -101,14 +94,6 @@ __global__ void k_vcf_lastkey(const uint8_t *__restrict__ text, const int64_t *_
         for (uint32_t k = 0; k < pl; ++k) key->pos[k] = text[ls + po + k];
         return;
     }
-}
-
-__device__ inline int wave_incl_scan(int x, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
 }
 
 // 0x80 in every byte of x that equals the byte b repeated in `pat` / that is below 0x21 -- exactly (no borrow between bytes)
@@ -166,7 +151,7 @@ __global__ __launch_bounds__(256) void k_vcf_cells(const uint8_t *__restrict__ t
                 bm &= valid & ~tm;
             }
             const int cnt = __popc(tm);
-            const int incl = wave_incl_scan(cnt, lane);
+            const int incl = pg_wave_incl_scan(cnt, lane);
             const int total = __shfl(incl, 63, 64);
             int r = n_tabs + incl - cnt;
             if (bm) {                                            // another blank among the columns the header names: str.split()'s business
@@ -199,7 +184,7 @@ __global__ __launch_bounds__(256) void k_vcf_cells(const uint8_t *__restrict__ t
             }
     }
     if (__builtin_amdgcn_ballot_w64(host) != 0) {
-        if (lane == 0) raise_host(status, (long long)i);
+        if (lane == 0) pg_raise_host(status, (long long)i);
         return;
     }
     // ---- (2) the selected samples' cells ----
@@ -240,7 +225,7 @@ __global__ __launch_bounds__(256) void k_vcf_cells(const uint8_t *__restrict__ t
             else if (cx) bytes = pgv_cell_bytes(L, cell, pl);
         }
         if (cx) {
-            const int incl = wave_incl_scan((int)bytes, lane);
+            const int incl = pg_wave_incl_scan((int)bytes, lane);
             const uint32_t at = run + (uint32_t)incl - bytes;
             run += (uint32_t)__shfl(incl, 63, 64);
             if (RENDER && active && !host) pgv_cell_put(t, L, cfg, cell, pl, true, s + 1 == n_sel, row + at);
@@ -248,14 +233,14 @@ __global__ __launch_bounds__(256) void k_vcf_cells(const uint8_t *__restrict__ t
             pgv_cell_put(t, L, cfg, cell, pl, false, s + 1 == n_sel, row + fixed_len + cell_off[s]);
     }
     if (__builtin_amdgcn_ballot_w64(host) != 0) {
-        if (lane == 0) raise_host(status, (long long)i);
+        if (lane == 0) pg_raise_host(status, (long long)i);
         return;
     }
     if (!RENDER && lane == 0) rlen[i] = run;
 }
 
 // the rows' places: exclusive sums of rlen over the lines (one block, every thread a stretch of lines), their total and number;
-// a total beyond the output buffer raises PGV_ST_OVERFLOW
+// a total beyond the output buffer raises PG_ST_OVERFLOW
 __global__ __launch_bounds__(1024) void k_vcf_scan(const uint32_t *__restrict__ rlen, int64_t n_lines, int64_t *__restrict__ roff,
                                                     long long *__restrict__ status, int64_t out_cap) {
     __shared__ long long sh[1024], shn[1024];
@@ -284,7 +269,7 @@ __global__ __launch_bounds__(1024) void k_vcf_scan(const uint32_t *__restrict__ 
     if (threadIdx.x == 1023) {
         status[2] = sh[1023];
         status[3] = shn[1023];
-        if (sh[1023] > out_cap) atomicOr(reinterpret_cast<unsigned long long *>(status), (unsigned long long)PGV_ST_OVERFLOW);
+        if (sh[1023] > out_cap) atomicOr(reinterpret_cast<unsigned long long *>(status), (unsigned long long)PG_ST_OVERFLOW);
     }
 }
 
@@ -440,7 +425,7 @@ extern "C" int pg_vcf_dev_parse(pg_ctx *c, int slot) {
     if ((rc = pg_tok_lines(c, slot, &n_lines)) != PG_OK) { V.state = 0; return rc; }
     if ((rc = V.status.ensure(8)) != PG_OK || (rc = V.h_status.ensure(8)) != PG_OK) return rc;
     if (!V.done) HIPCHK(hipEventCreateWithFlags(&V.done, hipEventDisableTiming));
-    V.h_status.p[0] = V.no_final_newline || n_lines == 0 ? PGV_ST_HOST : 0;     // (no line feed at all: one unfinished line)
+    V.h_status.p[0] = V.no_final_newline || n_lines == 0 ? PG_ST_HOST : 0;     // (no line feed at all: one unfinished line)
     V.h_status.p[1] = V.no_final_newline || n_lines == 0 ? 0 : 0x7fffffffffffffffll;
     V.h_status.p[2] = V.h_status.p[3] = V.h_status.p[4] = 0;
     if (D.cfg.flags & PGV_EXCLUDE_DUPLICATES) {                  // (the key this block starts from, for a block that goes to the host after all)
@@ -514,7 +499,7 @@ extern "C" int pg_vcf_dev_collect(pg_ctx *c, int slot, int64_t *out_len_out, int
     V.state = 0;
     if ((rc = pg_tok_crc_result(c, slot)) != PG_OK) return rc;
     if (V.h_status.p[0]) {
-        *host_line_out = (V.h_status.p[0] & PGV_ST_HOST) ? V.h_status.p[1] : 0;
+        *host_line_out = (V.h_status.p[0] & PG_ST_HOST) ? V.h_status.p[1] : 0;
         ++c->vcf.host_blocks;
         return PG_OK;
     }

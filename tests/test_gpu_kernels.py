@@ -407,6 +407,34 @@ def test_every_pairwise_code_path_gives_the_same_integers(mode, monkeypatch):
     e.close()
 
 
+DEAL_WINS = [(a, a + n) for a, n in zip(np.cumsum([0] + [64, 1500] * 9).tolist(), [64, 1500] * 9 + [64])]      # 19 consecutive windows
+
+
+@pytest.fixture(scope="module")
+def deal_oracle():
+    """the oracle's counts of the 19 windows (every case below takes a prefix of them)"""
+    e, lay, codes, _ = G.make_engine(40, 4, 19 * 1500, seed=1907)
+    e.close()
+    return [orc.pair_counts_gemm(oracle_aln(lay, codes, a, b)) for a, b in DEAL_WINS]
+
+
+@pytest.mark.parametrize("n_win", [1, 7, 8, 9, 16, 19])
+@pytest.mark.parametrize("mode", ["default", "PG_PAIR_VALU", "PG_PAIR_TILE=c", "PG_PAIR_TILE=none", "PG_PACK_FUSE=1"])
+def test_blocks_are_dealt_to_full_rows_of_eight_windows_and_to_the_rest(n_win, mode, deal_oracle, monkeypatch):
+    """the pair kernels' block dealing (csrc/pg_pair_common.h) on every kernel: no full row of eight windows, exactly one or two,
+    and one or two with a remainder; 40 diploids = two tiles of 32 units (several tasks per window in the one-wave kernels) and 80
+    haplotypes for D; windows of 64 sites (too short to be cut) alternate with windows of 1 500 (cut into parts when they are few)"""
+    G.set_mode(monkeypatch, mode)
+    e, lay, codes, _ = G.make_engine(40, 4, 19 * 1500, seed=1907)
+    wins = DEAL_WINS[:n_win]
+    D, C = e.batch([w[0] for w in wins], [w[1] for w in wins]).pairCounts(reference_order=True)
+    for k in range(n_win):
+        Do, Co = deal_oracle[k]
+        assert np.array_equal(C[k], Co), (mode, n_win, "C", k)
+        assert np.array_equal(D[k], Do), (mode, n_win, "D", k)
+    e.close()
+
+
 @pytest.mark.parametrize("n_dip", [31, 33, 64, 65, 97, 128, 129, 160, 161, 190, 193, 224])
 def test_called_counts_at_every_tile_count_of_the_one_wave_per_simd_kernel(n_dip):
     """k_pairC_big: one to seven tile rows (one wave up to 14 tiles, two beyond), windows shorter and longer than its LDS ring,

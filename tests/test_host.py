@@ -644,3 +644,17 @@ def test_format_float_rows_prints_what_numpy_prints(round_to):
     pre = ["a  ", "[2] 'bb'    ", "", "x", "yy "]
     want = "".join(p + " ".join(row) + "\n" for p, row in zip(pre, M.round(4).astype(str)))
     assert cli._float_rows(M, 4, pre) == want
+
+
+def test_the_pair_kernels_block_dealing_walked_as_a_program_of_its_own(tmp_path):
+    """tests/pair_deal_main.cpp: csrc/pg_pair_common.h's pg_deal_window over every block of pg_deal_blocks, n_win 0 .. 40 x per_win
+    1 .. 7, under AddressSanitizer and UndefinedBehaviorSanitizer: every (window, rest) exactly once, a window of a full row of
+    eight on the XCD win % 8, the remaining windows in one contiguous run of at most ceil(total / 8) per XCD"""
+    import subprocess
+    exe = str(tmp_path / "pair_deal_main")
+    # (the runtimes linked statically: the program is complete in itself, whatever else the environment loads into a process)
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "pair_deal_main.cpp"), "-o", exe])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0, (r.returncode, r.stdout.decode()[-2000:], r.stderr.decode()[-3000:])
+    assert r.stdout.decode().strip() == "%d cases, 0 bad" % (41 * 7)
