@@ -376,8 +376,7 @@ extern "C" int pg_set_samples(pg_ctx *c, int n_hap, const int32_t *hap_pop, cons
     c->n_samp = (int)sstart.size() - 1;
     c->S = (n_hap + 15) / 16 * 16;
     c->RS = pg_nib_pitch(c->S);
-    // plane stride: 32 haplotypes (one tile of the matrix-core pair kernels); the popcount kernels work on 64-lane column chunks
-    c->NP = getenv("PG_PAIR_VALU") ? (n_hap + 63) / 64 * 64 : (n_hap + 31) / 32 * 32;
+    c->NP = pg_plane_stride(n_hap, pg_pair_switches());
     c->h_pop_start = pstart;
     c->h_samp_start = sstart;
     {   // the reference's row order / population rank: identity until pg_set_reference_order
@@ -790,70 +789,28 @@ static int stage_windows(pg_ctx *c, const int64_t *lo, const int64_t *hi, int w0
 // `consume` of sub-batch k run on ctx->stream (two slots of planes).  `consume(batch_w0, batch_n)` is called with the
 // batch's matrices queued on ctx->stream: D in ctx->Dmat ([N][N] per window, upper triangle) and the called counts in
 // ctx->Cmat ([cN][cN] per window, upper triangle, entry of haplotypes (i,j) at (i>>cshift, j>>cshift)).
+// What is decided -- routes, batches, the staging vector, the scratch sizes -- is decided in pg_pair_plan.h; this carries it out.
 template <class F>
 static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_win, bool dip, F consume) {
-    const int N = c->n_hap, NP = c->NP;
-    const int n_units = dip ? N / 2 : N;
-    const int NPv = dip ? (NP % 64 ? (n_units + 31) / 32 * 32 : (n_units + 63) / 64 * 64) : NP;
+    const PgPairSwitches sw = pg_pair_switches();
+    const PgPairShape s = pg_pair_shape(c->n_hap, c->NP, dip);
+    const PgPairPlan plan = pg_plan_pair_pass(s, sw, lo, hi, n_win, c->scratch_limit, c->xv_worst);
+    const int N = s.N, NP = s.NP, NPv = s.NPv, n_units = s.n_units, grp = plan.grp, capg = plan.capg, diag = dip ? 1 : 0;
     c->cN = n_units;
     c->cshift = dip ? 1 : 0;
-    const int64_t mat_bytes = 4ll * N * N + 4ll * n_units * n_units;
-    // compaction group = words per pack block: 128 when that still oversubscribes the chip's wave slots several times (see
-    // pg_internal.h), else 64, and 32 when 64 would leave fewer than two waves per SIMD slot (C2: 4883 one-wave blocks; measured
-    // 0.44 - 0.47 ms with 32 against 0.465 - 0.484 with 64); PG_GROUP_WORDS overrides (A/B runs)
-    int grp = PG_GROUP;
-    {
-        int64_t blocks64 = 0;
-        for (int w = 0; w < n_win; ++w) blocks64 += ((hi[w] - lo[w] + 31) / 32 + PG_GROUP - 1) / PG_GROUP;
-        const int waves_per_block = (NP / 4 + 63) / 64;
-        if (blocks64 * waves_per_block >= 32768) grp = PG_GROUP_MAX;
-        else if (blocks64 * waves_per_block < 8192) grp = PG_GROUP / 2;
-        if (const char *g = getenv("PG_GROUP_WORDS")) grp = std::min(PG_GROUP_MAX, std::max(8, atoi(g) / 4 * 4));
-    }
-    // scratch bytes per 32-site input word of one slot: called plane + reserved virtual-site planes (capg words per group)
-    const int capg = c->xv_worst ? PG_XV_CAP(grp) : PG_XV_CAP_DEFAULT(grp);
-    // the fused form of the pack kernel counts the called pairs itself: no called plane, no C-count kernel (pg_pair2.hip)
-    const bool fused = pg_pack_fuse_fits(NP, NPv, n_units, n_win);
-    const int64_t word_bytes = ((int64_t)NP * 4 * PG_XV_PLANES * capg + grp - 1) / grp + (fused ? 0 : (int64_t)NPv * 4);
-    // sub-batch size: at most half the scratch budget per slot (and, for the two-stream pipeline, at least ~8 sub-batches per
-    // call, but none so small that it cannot fill the GPU)
-    int64_t total_words_all = 0;
-    for (int w = 0; w < n_win; ++w) total_words_all += ((hi[w] - lo[w] + 31) / 32 + grp - 1) / grp * grp;
-    // A job that fits one batch runs as one batch on one stream: splitting it only to overlap the pack kernel with the pair
-    // kernels is slower (measured: C2 1.44 vs 0.99 ms).  A job that needs several batches is cut at the scratch limit and its
-    // sub-batches follow each other on the one stream: since the pair kernels run on the matrix cores, the pack kernel beside
-    // them on a second stream costs more CU time than it hides (north-star shape 11.2 - 12.1 against 9.8 - 11.0 ms; one rank's
-    // share of config 5, 150 GB: 40.1 ms pipelined).  PG_OVERLAP=1 brings the two-stream pipeline back (at least 8 sub-batches,
-    // all but the first pack kernel beside the pair kernels of the sub-batch before).
-    // (one batch uses one slot: it may take the whole scratch budget; sub-batches alternate between the two slots)
-    const bool multi = total_words_all * word_bytes + (int64_t)n_win * mat_bytes > c->scratch_limit;
-    const bool two_streams = getenv("PG_OVERLAP") != nullptr;
-    const int n_sub = two_streams && atoi(getenv("PG_OVERLAP")) >= 2 ? atoi(getenv("PG_OVERLAP")) : 8;      // (PG_OVERLAP=n: n sub-batches)
-    const bool split = multi || two_streams;
-    int64_t target_words = two_streams ? std::max<int64_t>(total_words_all / n_sub, 32768) : total_words_all;
     for (int k = 0; k < 2; ++k) {
         if (!c->slot[k].packed) HIPCHK(hipEventCreateWithFlags(&c->slot[k].packed, hipEventDisableTiming));
         if (!c->slot[k].consumed) HIPCHK(hipEventCreateWithFlags(&c->slot[k].consumed, hipEventDisableTiming));
         c->slot[k].used = false;
     }
-    int w0 = 0, bi = 0;
-    while (w0 < n_win) {
-        int64_t words = 0;
-        int w1 = w0;
-        while (w1 < n_win) {
-            int64_t wlen = ((hi[w1] - lo[w1] + 31) / 32 + grp - 1) / grp * grp;
-            int64_t nbytes = (words + wlen) * word_bytes + (int64_t)(w1 - w0 + 1) * mat_bytes;
-            if (w1 > w0 && (nbytes > (split ? c->scratch_limit / 2 : c->scratch_limit) || words + wlen > target_words)) break;
-            words += wlen;
-            ++w1;
-            if (w1 - w0 >= 65535) break;                      // gridDim.y limit
-        }
-        const int nb = w1 - w0;
+    for (int w0 = 0, bi = 0; w0 < n_win; ++bi) {
+        PgBatchLayout L = pg_cut_batch(plan, lo, hi, n_win, w0);
+        const int nb = L.nb, w1 = w0 + nb;
         pg_ctx::Slot &sl = c->slot[bi & 1];
         int rc;
         // one batch, or sub-batches one after the other: the pack kernel goes on the same stream as its consumers
         // (no cross-stream event hand-over)
-        const bool single = (w0 == 0 && w1 == n_win) || !two_streams;
+        const bool single = (w0 == 0 && w1 == n_win) || !plan.two_streams;
         hipStream_t ps = single ? c->stream : c->stream2;
         // the slot's previous occupant (sub-batch bi-2) must be fully consumed before its planes are overwritten, and
         // its staging vector must have been copied before it is rebuilt
@@ -861,42 +818,15 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
             HIPCHK(hipStreamWaitEvent(ps, sl.consumed, 0));
             HIPCHK(hipEventSynchronize(sl.packed));
         }
-        // stage [lo | hi | goff(n+1) | vgoff(n+1) | nw]: nw = int32 word counters of k_pack2, zero per window (and, in the
-        // presence-pre-pass mode, one slot per group for k_word_scan) -- they ride in the same copy instead of a memset
-        int64_t ga_pre = 0;
-        for (int k = 0; k < nb; ++k) ga_pre += ((hi[w0 + k] - lo[w0 + k] + 31) / 32 + grp - 1) / grp;
-        const size_t n_nw = (size_t)nb + (pg_pack_needs_presence(NP) ? (size_t)ga_pre : 0);
-        const size_t h_len = 4 * (size_t)nb + 2 + (n_nw + 1) / 2;
-        if ((rc = sl.host.ensure(h_len)) != PG_OK) return rc;
-        int64_t *h = sl.host.p;
-        int64_t ga = 0, va = 0;
-        int max_groups = 0;
-        int64_t max_wds = 0, sum_wds = 0;
-        for (int k = 0; k < nb; ++k) {
-            h[k] = lo[w0 + k];
-            h[nb + k] = hi[w0 + k];
-            const int64_t wds = (hi[w0 + k] - lo[w0 + k] + 31) / 32;
-            max_wds = std::max(max_wds, wds);
-            sum_wds += wds;
-            h[2 * (size_t)nb + k] = ga;
-            h[3 * (size_t)nb + 1 + k] = va;
-            const int64_t groups = (wds + grp - 1) / grp;
-            ga += groups;
-            va += (wds + 3) / 4;
-            max_groups = (int)std::max<int64_t>(max_groups, groups);
-        }
-        h[3 * (size_t)nb] = ga;
-        h[4 * (size_t)nb + 1] = va;
-        memset(h + 4 * (size_t)nb + 2, 0, ((n_nw + 1) / 2) * 8);
-        if ((rc = sl.win.upload(h, h_len, ps)) != PG_OK) return rc;
-        const int64_t *d_lo = sl.win.p, *d_hi = sl.win.p + nb, *d_goff = sl.win.p + 2 * (size_t)nb,
-                      *d_vgoff = sl.win.p + 3 * (size_t)nb + 1;
-        int32_t *d_nw = reinterpret_cast<int32_t *>(sl.win.p + 4 * (size_t)nb + 2);
-        // + 4 word groups / words: the last stage (look-ahead load) of the pair kernels reads up to three past a part's range
-        if (!fused && (rc = sl.Vp.ensure((size_t)(std::max<int64_t>(va, 1) + 4) * NPv * 4)) != PG_OK) return rc;
-        if ((rc = sl.XV.ensure(((size_t)std::max<int64_t>(ga, 1) * capg + 4) * PG_XV_PLANES * NP)) != PG_OK) return rc;
-        if ((rc = c->Cmat.ensure((size_t)nb * n_units * n_units)) != PG_OK) return rc;
-        if ((rc = c->Dmat.ensure((size_t)nb * N * N)) != PG_OK) return rc;
+        if ((rc = sl.host.ensure(L.h_len)) != PG_OK) return rc;
+        pg_batch_fill(L, plan, s, lo, hi, sl.host.p);
+        if ((rc = sl.win.upload(sl.host.p, L.h_len, ps)) != PG_OK) return rc;
+        const int64_t *d_lo = sl.win.p, *d_hi = sl.win.p + L.off_hi, *d_goff = sl.win.p + L.off_goff, *d_vgoff = sl.win.p + L.off_vgoff;
+        int32_t *d_nw = reinterpret_cast<int32_t *>(sl.win.p + L.off_nw);
+        if (L.n_Vp && (rc = sl.Vp.ensure(L.n_Vp)) != PG_OK) return rc;
+        if ((rc = sl.XV.ensure(L.n_XV)) != PG_OK) return rc;
+        if ((rc = c->Cmat.ensure(L.n_Cmat)) != PG_OK) return rc;
+        if ((rc = c->Dmat.ensure(L.n_Dmat)) != PG_OK) return rc;
         hipEvent_t e0, e1;
         // ---- stream2: pack ----
         const bool time_pack = (c->time_mask >> PG_K_PACK) & 1u;
@@ -905,14 +835,14 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
             if ((rc = event_get(c, &e1)) != PG_OK) return rc;
             HIPCHK(hipEventRecord(e0, ps));
         }
-        if (pg_pack_needs_presence(NP) && (rc = sl.pres.ensure((size_t)std::max<int64_t>(ga, 1) * grp * 4)) != PG_OK) return rc;
-        if (fused) {
-            if (pg_launch_pack_fused(ps, c->gt.p, c->RS, d_lo, d_hi, d_goff, nb, max_wds, sum_wds / nb, sl.XV.p, NP, d_nw, dip ? 1 : 0,
-                                     c->flag.p, capg, n_units, c->Cmat.p))
+        if (L.n_pres && (rc = sl.pres.ensure(L.n_pres)) != PG_OK) return rc;
+        if (plan.fused()) {
+            if (pg_launch_pack_fused(ps, c->gt.p, c->RS, d_lo, d_hi, d_goff, nb, L.max_wds, L.sum_wds / nb, sl.XV.p, NP, d_nw, diag, c->flag.p, capg,
+                                     n_units, c->Cmat.p))
                 return pg_fail(PG_ERR_HIP, "the fused pack kernel was refused its LDS");
         } else
-            pg_launch_pack2(ps, c->gt.p, c->RS, d_lo, d_hi, d_goff, d_vgoff, nb, max_groups, ga, sl.Vp.p, NPv, sl.XV.p, NP,
-                            d_nw, dip ? 1 : 0, c->flag.p, sl.pres.p, capg, grp);
+            pg_launch_pack2(ps, c->gt.p, c->RS, d_lo, d_hi, d_goff, d_vgoff, nb, L.max_groups, L.ga, sl.Vp.p, NPv, sl.XV.p, NP, d_nw, diag, c->flag.p,
+                            sl.pres.p, capg, grp, plan.pack, sw);
         if (time_pack) {
             HIPCHK(hipEventRecord(e1, ps));
             c->events[PG_K_PACK].push_back(std::make_pair(e0, e1));
@@ -921,27 +851,29 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
         HIPCHK(hipEventRecord(sl.packed, ps));
         // ---- stream: pair kernels + consume ----
         if (!single) HIPCHK(hipStreamWaitEvent(c->stream, sl.packed, 0));
-        if (!fused && (rc = pg_time_begin(c, PG_K_PAIRWISE, &e0, &e1)) != PG_OK) return rc;
-        // the pair counts run on the matrix cores (exact products of the bit planes, pg_pair_mfma.hip: MX fp4, or int8 with
-        // PG_PAIR_I8=1); PG_PAIR_VALU=1 keeps the popcount kernels (A/B runs, tests)
-        const bool valu_pairs = getenv("PG_PAIR_VALU") != nullptr;
-        if (valu_pairs && NP % 64) return pg_fail(PG_ERR_STATE, "PG_PAIR_VALU must be set before pg_set_samples (plane stride %d)", NP);
-        if (fused) {
-            // (C is in Cmat already)
-        } else if (!valu_pairs && pg_pair_big_fits(NPv, n_units)) {
-            pg_launch_pairC_big(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, dip ? 1 : 0, va / nb, (int64_t)max_groups * grp * 32, c->Cmat.p);
-        } else if (!valu_pairs && pg_pair_tile_fits(NPv)) {
-            if (pg_launch_pairC_tile(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, dip ? 1 : 0, va / nb, (int64_t)max_groups * grp * 32, c->Cmat.p))
-                return pg_fail(PG_ERR_HIP, "pair-kernel program upload failed");
-        } else if (!valu_pairs) pg_launch_pairC_mfma(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, dip ? 1 : 0, va / nb, (int64_t)max_groups * grp * 32, c->Cmat.p);
-        else if (dip) pg_launch_pairC(c->stream, sl.Vp.p, d_vgoff, nb, c->tasksC.p, c->n_tasksC, NPv, n_units, 1, va / nb, c->Cmat.p);
-        else pg_launch_pairC(c->stream, sl.Vp.p, d_vgoff, nb, c->tasksCh.p, c->n_tasksCh, NPv, n_units, 0, va / nb, c->Cmat.p);
-        if (!fused && (rc = pg_time_end(c, PG_K_PAIRWISE, e0, e1, 1)) != PG_OK) return rc;
+        if (!plan.fused() && (rc = pg_time_begin(c, PG_K_PAIRWISE, &e0, &e1)) != PG_OK) return rc;
+        if (sw.valu && NP % 64) return pg_fail(PG_ERR_STATE, "PG_PAIR_VALU must be set before pg_set_samples (plane stride %d)", NP);
+        const int64_t avg_wq = L.va / nb, max_sites = (int64_t)L.max_groups * grp * 32;
+        switch (plan.c_route) {
+            case PG_C_IN_PACK: break;                         // (C is in Cmat already)
+            case PG_C_BIG: pg_launch_pairC_big(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, diag, avg_wq, max_sites, c->Cmat.p); break;
+            case PG_C_TILE:
+                if (pg_launch_pairC_tile(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, diag, avg_wq, max_sites, c->Cmat.p))
+                    return pg_fail(PG_ERR_HIP, "pair-kernel program upload failed");
+                break;
+            case PG_C_FP4: pg_launch_pairC_mfma(c->stream, sl.Vp.p, d_vgoff, nb, NPv, n_units, diag, avg_wq, max_sites, c->Cmat.p); break;
+            case PG_C_POPCOUNT:
+                pg_launch_pairC(c->stream, sl.Vp.p, d_vgoff, nb, dip ? c->tasksC.p : c->tasksCh.p, dip ? c->n_tasksC : c->n_tasksCh, NPv, n_units, diag,
+                                avg_wq, c->Cmat.p);
+                break;
+        }
+        if (!plan.fused() && (rc = pg_time_end(c, PG_K_PAIRWISE, e0, e1, 1)) != PG_OK) return rc;
         // (running k_pairD beside k_pairC on a third stream was measured: +3 % throughput, but overlapping kernels make the
         // per-kernel timings ambiguous; kept sequential)
         if ((rc = pg_time_begin(c, PG_K_PAIRD, &e0, &e1)) != PG_OK) return rc;
-        if (!valu_pairs) pg_launch_pairD_mfma(c->stream, sl.XV.p, d_nw, d_goff, nb, NP, N, ga / nb * grp / 10, (int64_t)max_groups * capg * 32, c->Dmat.p, capg);
-        else pg_launch_pairD(c->stream, sl.XV.p, d_nw, d_goff, nb, c->tasks2.p, c->n_tasks2, NP, N, ga / nb, c->Dmat.p, capg);
+        if (plan.d_route == PG_D_FP4)
+            pg_launch_pairD_mfma(c->stream, sl.XV.p, d_nw, d_goff, nb, NP, N, L.ga / nb * grp / 10, (int64_t)L.max_groups * capg * 32, c->Dmat.p, capg);
+        else pg_launch_pairD(c->stream, sl.XV.p, d_nw, d_goff, nb, c->tasks2.p, c->n_tasks2, NP, N, L.ga / nb, c->Dmat.p, capg);
         if ((rc = pg_time_end(c, PG_K_PAIRD, e0, e1, 1)) != PG_OK) return rc;
         HIPCHK(hipGetLastError());
         c->cur_win_lo = d_lo;
@@ -950,7 +882,6 @@ static int pairwise_batches(pg_ctx *c, const int64_t *lo, const int64_t *hi, int
         HIPCHK(hipEventRecord(sl.consumed, c->stream));
         sl.used = true;
         w0 = w1;
-        ++bi;
     }
     // leave both streams quiescent with respect to each other: later work on ctx->stream must see stream2's writes done
     for (int k = 0; k < 2; ++k)
@@ -1009,7 +940,7 @@ static int note_flags(pg_ctx *c, int flag, bool *dip, bool *again) {
 
 template <class F>
 static int pairwise_run(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_win, F consume) {
-    bool dip = c->all_diploid && getenv("PG_NO_DIP") == nullptr;
+    bool dip = pg_start_dip(c->all_diploid, pg_pair_switches());
     int rc;
     if ((rc = flag_ready(c)) != PG_OK) return rc;
     for (;;) {
@@ -1037,6 +968,40 @@ int pg_pairwise_each(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_win,
 // time on the freshly zeroed buffer predicts its time with the data in place (probe 7.4-7.5 -> 7.8-7.9 ms, probe 8.0-8.4 -> 8.3-8.6),
 // so a large reservation is tried a few times -- the candidates are held together, so they are different pages -- and the one on
 // which the probe pass (the regular pack + pair path over 50 000-site windows of the empty rows) is fastest is kept.
+// The probe of both tuners: the regular pack + pair path over n_win windows of `wind` sites of the first n_sites rows, timed by
+// events on ctx->stream and kept out of the caller's kernel statistics while the probe lives.
+struct PlacementProbe {
+    pg_ctx *c;
+    std::vector<int64_t> lo, hi;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const uint32_t saved_mask;
+    int rc = PG_OK;
+    PlacementProbe(pg_ctx *ctx, int64_t n_sites, int64_t wind, int n_win) : c(ctx), lo((size_t)n_win), hi((size_t)n_win), saved_mask(ctx->time_mask) {
+        for (int w = 0; w < n_win; ++w) { lo[(size_t)w] = w * wind; hi[(size_t)w] = std::min<int64_t>(n_sites, (w + 1) * wind); }
+        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) rc = pg_fail(PG_ERR_HIP, "hipEventCreate");
+        c->time_mask = 0;
+    }
+    // `passes` passes: the first also allocates the scratch and does not count; *ms_out = the fastest of the others (two passes:
+    // the last one, pg_reserve_sites_tuned's rule; three: the faster of the last two, pg_tune_planes')
+    int run(int passes, float *ms_out) {
+        float ms = 0.0f;
+        for (int pass = 0; pass < passes; ++pass) {
+            if (hipEventRecord(e0, c->stream) != hipSuccess) return pg_fail(PG_ERR_HIP, "hipEventRecord");
+            int r = pairwise_run(c, lo.data(), hi.data(), (int)lo.size(), [](int, int) -> int { return PG_OK; });
+            if (r != PG_OK) return r;
+            if (hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
+                hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return pg_fail(PG_ERR_HIP, "probe timing");
+            if (pass == 1 || (pass > 1 && ms < *ms_out)) *ms_out = ms;
+        }
+        return PG_OK;
+    }
+    ~PlacementProbe() {
+        c->time_mask = saved_mask;
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
 extern "C" int pg_reserve_sites_tuned(pg_ctx *c, int64_t n_sites, int max_trials, double *probe_ms_out, int *n_trials_out,
                                       int *chosen_out) {
     if (!c) return pg_fail(PG_ERR_ARG, "null ctx");
@@ -1063,22 +1028,15 @@ extern "C" int pg_reserve_sites_tuned(pg_ctx *c, int64_t n_sites, int max_trials
     }
     if (trials < 2) return pg_reserve_sites(c, n_sites);
     const int64_t wind = 50000;
-    const int n_win = (int)std::max<int64_t>(1, n_sites / wind);
-    std::vector<int64_t> lo((size_t)n_win), hi((size_t)n_win);
-    for (int w = 0; w < n_win; ++w) { lo[(size_t)w] = w * wind; hi[(size_t)w] = std::min<int64_t>(n_sites, (w + 1) * wind); }
+    PlacementProbe probe(c, n_sites, wind, (int)std::max<int64_t>(1, n_sites / wind));
     std::vector<DevBuf<int8_t>> cand((size_t)trials);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = PG_OK, best = -1, tried = 0;
     double best_ms = 0.0;
     auto cleanup = [&](int keep_idx) {
         for (int t = 0; t < trials; ++t)
             if (t != keep_idx) cand[(size_t)t].release();
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
     };
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { cleanup(-1); return pg_fail(PG_ERR_HIP, "hipEventCreate"); }
-    const uint32_t saved_mask = c->time_mask;
-    c->time_mask = 0;                                      // the probe's launches are not the caller's statistics
+    if ((rc = probe.rc) != PG_OK) { cleanup(-1); return rc; }
     for (int t = 0; t < trials && rc == PG_OK; ++t) {
         if (cand[(size_t)t].alloc(bytes) != PG_OK) break;  // out of memory: make do with the candidates so far
         ++tried;
@@ -1086,18 +1044,10 @@ extern "C" int pg_reserve_sites_tuned(pg_ctx *c, int64_t n_sites, int max_trials
         c->gt = cand[(size_t)t];                           // (plain pointers: ownership stays with cand[] until the choice is made)
         c->cap_sites = n_sites;
         float ms = 0.0f;
-        for (int pass = 0; pass < 2 && rc == PG_OK; ++pass) {                 // the first pass also allocates the scratch
-            if (hipEventRecord(e0, c->stream) != hipSuccess) { rc = pg_fail(PG_ERR_HIP, "hipEventRecord"); break; }
-            rc = pairwise_run(c, lo.data(), hi.data(), n_win, [](int, int) -> int { return PG_OK; });
-            if (rc != PG_OK) break;
-            if (hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { rc = pg_fail(PG_ERR_HIP, "probe timing"); break; }
-        }
-        if (rc != PG_OK) break;
+        if ((rc = probe.run(2, &ms)) != PG_OK) break;
         if (probe_ms_out) probe_ms_out[t] = ms;
         if (best < 0 || ms < best_ms) { best = t; best_ms = ms; }
     }
-    c->time_mask = saved_mask;
     c->gt = DevBuf<int8_t>();
     c->cap_sites = 0;
     if (rc != PG_OK || best < 0) {
@@ -1131,9 +1081,7 @@ extern "C" int pg_tune_planes(pg_ctx *c, int64_t n_sites, int64_t window_sites, 
     if (trials < 2) return PG_OK;
     const int64_t wind = window_sites > 0 ? window_sites : 50000;
     if ((n_sites + wind - 1) / wind > (1 << 24)) return pg_fail(PG_ERR_ARG, "pg_tune_planes: more than 2^24 windows");
-    const int n_win = (int)((n_sites + wind - 1) / wind);
-    std::vector<int64_t> lo((size_t)n_win), hi((size_t)n_win);
-    for (int w = 0; w < n_win; ++w) { lo[(size_t)w] = w * wind; hi[(size_t)w] = std::min<int64_t>(n_sites, (w + 1) * wind); }
+    PlacementProbe probe(c, n_sites, wind, (int)((n_sites + wind - 1) / wind));
     struct Set { DevBuf<uint32_t> Vp[2], XV[2]; };
     std::vector<Set> cand((size_t)trials);
     auto take = [&](Set &s) {                                 // the slots' planes -> s (plain pointers; the slots are left without)
@@ -1152,14 +1100,8 @@ extern "C" int pg_tune_planes(pg_ctx *c, int64_t n_sites, int64_t window_sites, 
             s.XV[k] = DevBuf<uint32_t>();
         }
     };
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
-        return pg_fail(PG_ERR_HIP, "hipEventCreate");
-    }
-    const uint32_t saved_mask = c->time_mask;
-    c->time_mask = 0;                                         // the probe's launches are not the caller's statistics
-    int rc = PG_OK, best = -1, tried = 0;
+    int rc = probe.rc, best = -1, tried = 0;
+    if (rc != PG_OK) return rc;
     double best_ms = 0.0;
     size_t set_bytes = 0;
     for (int t = 0; t < trials && rc == PG_OK; ++t) {
@@ -1168,15 +1110,8 @@ extern "C" int pg_tune_planes(pg_ctx *c, int64_t n_sites, int64_t window_sites, 
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * set_bytes + ((size_t)8 << 30)) break;
         }
-        float ms = 0.0f, fastest = 0.0f;
-        for (int pass = 0; pass < 3 && rc == PG_OK; ++pass) {                 // the first pass allocates; the faster of the next two counts
-            if (hipEventRecord(e0, c->stream) != hipSuccess) { rc = pg_fail(PG_ERR_HIP, "hipEventRecord"); break; }
-            rc = pairwise_run(c, lo.data(), hi.data(), n_win, [](int, int) -> int { return PG_OK; });
-            if (rc != PG_OK) break;
-            if (hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess ||
-                hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { rc = pg_fail(PG_ERR_HIP, "probe timing"); break; }
-            if (pass == 1 || (pass == 2 && ms < fastest)) fastest = ms;
-        }
+        float fastest = 0.0f;
+        rc = probe.run(3, &fastest);
         if (rc != PG_OK) {
             if (t > 0 && rc == PG_ERR_HIP) {               // out of memory: make do with the candidates so far
                 rc = PG_OK;
@@ -1193,9 +1128,6 @@ extern "C" int pg_tune_planes(pg_ctx *c, int64_t n_sites, int64_t window_sites, 
         if (probe_ms_out) probe_ms_out[t] = fastest;
         if (best < 0 || fastest < best_ms) { best = t; best_ms = fastest; }
     }
-    c->time_mask = saved_mask;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(c->stream2);
     if (best >= 0) give(cand[(size_t)best]);
@@ -1471,7 +1403,7 @@ extern "C" int pg_popdist_stats(pg_ctx *c, const int64_t *lo, const int64_t *hi,
         HIPCHK(hipGetLastError());
         return PG_OK;
     };
-    bool dip = c->all_diploid && getenv("PG_NO_DIP") == nullptr;
+    bool dip = pg_start_dip(c->all_diploid, pg_pair_switches());
     const size_t n_out = (size_t)n_win * ncols;
     if ((rc = c->out_pin.ensure(n_out + 1)) != PG_OK) return rc;
     // one device-to-host copy (into pinned memory) and one synchronisation per pass: the flag word of the pack kernels (diploid

@@ -4,26 +4,13 @@
 #include <stdint.h>
 #include "../../include/popgen_hip.h"
 #include "pg_nib.h"
+#include "pg_pair_plan.h"     // PG_XV_PLANES, PG_GROUP, PG_XV_CAP; the routes and switches of the pack-and-pair pass
 
 #define PG_MAX_POPS 16          // populations handled by the site-statistics kernels (K3/K6 take any number)
 #define PG_SITES_PER_BLOCK 1024 // sites reduced by one block of the site-statistics kernels
 #define PG_ABBA_SITES_PER_BLOCK 4096   // k_abba_q: fewer, longer blocks (prologue masks + epilogue reduction per block)
 #define PG_ABBA_NSUM 6
 #define PG_FOURPOP_NSUM 14
-#define PG_XV_PLANES 2        // planes per word of virtual biallelic sites: x ("carries the tested allele"), v (called, not excluded)
-
-// Input words (of 32 sites) per compaction group of the pack kernels = per block: 64 (2048 sites), or 128 when that still leaves
-// the chip several times oversubscribed with blocks (pg_pick_group): larger groups end in fewer partial XV words (k_pairD's work)
-// and amortise a block's start-up; measured on the north-star shape (50 000 -> 25 000 two-wave blocks): k_pack3 -5 %, k_pairD
-// -3.5 %; on C2 (5000 -> 2600 one-wave blocks, fewer than the chip holds) k_pack3 +5 %.
-#define PG_GROUP 64
-#define PG_GROUP_MAX 128
-// words of virtual sites reserved per group: worst case (every site with four alleles) / default
-// Words reserved per group by default: enough whenever a window has no more virtual sites than sites (a biallelic site is
-// one virtual site; + 1 for the group's partial last word).  k_pack2 / k_pack3 raise bit 1 of the flag word when a window needs
-// more; the host then repeats the call with PG_XV_CAP (and keeps that reservation for the rest of the context's life).
-#define PG_XV_CAP(grp) (3 * (grp))
-#define PG_XV_CAP_DEFAULT(grp) ((grp) + 1)
 // windows of up to this many sites get their float64 sums in NumPy's order (k_popdist_np, k_quartet_np): quotients and products of
 // small integers sit on rounding ties of the printed digit, differences of equal means are +-0.0
 #define PG_NP_MAX_SITES 256
@@ -88,18 +75,12 @@ void pg_launch_hap_called(hipStream_t st, const int8_t *gt, int RS, int n_hap, c
                           const int64_t *win_hi, int n_win, int max_chunks, unsigned long long *out);
 
 // ---- pairwise pipeline (pg_pair2.hip) ---------------------------------------------------------------
+// the two-kernel pack path: k_pack3, k_pack2, or k_pack2 behind the presence pre-pass, as `route` says
 void pg_launch_pack2(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi,
                      const int64_t *goff, const int64_t *vgoff, int n_win, int max_groups, int64_t total_groups, uint32_t *Vp,
-                     int NPv, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch, uint32_t *pres, int capg, int grp);
-bool pg_pack_needs_presence(int NP);
-// the fused form of k_pack3: pack and called counts in one kernel, no called plane (pg_pair2.hip); launch: 0 = launched
-struct PgFuseArgs {
-    int32_t n_win, kparts, n_units, T, diag;
-    int32_t *Cmat;
-    signed char a[8][4], b[8][2];           // wave w forms the tiles (a[w][p], b[w][p & 1]), p = 0 .. 3, of those mask[w] names
-    unsigned char mask[8];
-};
-bool pg_pack_fuse_fits(int NP, int NPv, int n_units, int n_win);
+                     int NPv, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch, uint32_t *pres, int capg, int grp,
+                     PgPackRoute route, const PgPairSwitches &sw);
+// the fused form of k_pack3 (PgFuseArgs, pg_pair_plan.h); launch: 0 = launched
 int pg_launch_pack_fused(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi, const int64_t *goff,
                          int n_win, int64_t max_words, int64_t avg_words, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch,
                          int capg, int n_units, int32_t *Cmat);
@@ -116,12 +97,10 @@ void pg_launch_pairD_mfma(hipStream_t st, const uint32_t *XV, const int32_t *nw,
                           int64_t avg_words, int64_t max_vsites, int32_t *Dmat, int capg);
 
 // the called-count products with the planes staged through LDS, one block per window part (pg_pair_tile.hip); 0 = launched
-bool pg_pair_tile_fits(int NPv);
 int pg_launch_pairC_tile(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, int n_win, int NPv, int n_units, int diag,
                          int64_t avg_wq, int64_t max_sites, int32_t *Cmat);
 
 // called counts with one wave per SIMD and up to 14 tiles per wave (pg_pair_big.hip): planes of up to 224 units
-bool pg_pair_big_fits(int NPv, int n_units);
 void pg_launch_pairC_big(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, int n_win, int NPv, int n_units, int diag,
                          int64_t avg_wq, int64_t max_sites, int32_t *Cmat);
 

@@ -1009,34 +1009,25 @@ __global__ __launch_bounds__(TPB) void k_pack3(const int8_t *__restrict__ gt, in
 template <int DIP>
 static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *gt, int RS, const int64_t *win_lo,
                          const int64_t *win_hi, const int64_t *goff, const int64_t *vgoff, uint32_t *Vp, int NPv, uint32_t *XV,
-                         int NP, int32_t *nw, int32_t *mismatch, uint32_t *pres, int capg, int grp) {
-    // Up to 4096 slots: k_pack3 (one block of up to 16 waves per group; every row fetched once; PMC: 2.27 instead of 2.56 GB per C2 pass, 44.5 instead of 49.2 GB per
-    // north-star pass).  Same-box A/B (profiles/r02/ab_pack_*.txt): C2 0.450-0.485 vs 0.457-0.463 ms, north-star shape 7.7-7.9 vs
-    // 8.0-9.2 ms -- once the per-entry allele look-up had moved from the scalar unit to a lane-parallel table (before that
-    // k_pack3 lost on two-wave blocks, 8.3-9.0 ms: every wave of a block runs the per-entry scalar loop).  More than 4096 slots:
-    // k_pack2 behind the presence pre-pass (round 2 took that route from 1024 slots on: C4 read its rows twice, 0.27 of HBM).
-    // PG_PACK2=1 forces k_pack2 (A/B runs and tests).
+                         int NP, int32_t *nw, int32_t *mismatch, uint32_t *pres, int capg, int grp, PgPackRoute route,
+                         const PgPairSwitches &sw) {
+    // Who packs which shape is pg_pack_route's decision (pg_pair_plan.h); why: up to 4096 slots k_pack3 (one block of up to 16 waves
+    // per group; every row fetched once; PMC: 2.27 instead of 2.56 GB per C2 pass, 44.5 instead of 49.2 GB per north-star pass).
+    // Same-box A/B (profiles/r02/ab_pack_*.txt): C2 0.450-0.485 vs 0.457-0.463 ms, north-star shape 7.7-7.9 vs 8.0-9.2 ms -- once the
+    // per-entry allele look-up had moved from the scalar unit to a lane-parallel table (before that k_pack3 lost on two-wave blocks,
+    // 8.3-9.0 ms: every wave of a block runs the per-entry scalar loop).  More than 4096 slots: k_pack2 behind the presence pre-pass
+    // (round 2 took that route from 1024 slots on: C4 read its rows twice, 0.27 of HBM).  PG_PACK2=1 forces k_pack2 (A/B runs, tests).
     // (k_pack3: a lane covers 8 slots = one dword of a resident row, threads / 2 lanes; k_pack2: 4 slots, `threads`)
-    const bool force2 = getenv("PG_PACK2") != nullptr;
-    if (threads <= 1024 && !force2) {
+    if (route == PG_PACK_3) {
         const int lanes = (threads + 1) / 2;
 #define PG_PACK3B(T, B) hipLaunchKernelGGL((k_pack3<T, DIP, B, 0>), grid, dim3(T), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, capg, grp, fq, perm, PgFuseArgs())
 #define PG_PACK3(T) PG_PACK3B(T, 0)
         // quadruples of the called plane per burst (the rest of the 24 LDS cells per thread holds virtual-site words: two)
         const int fq = DIP ? 4 : 2;
-        // PG_PACK_PERM=k (experiment): windows in the order 0, P, 2P, ... (mod n), P the number coprime with n next to n / k
-        int perm = 1;
-        if (const char *pe = getenv("PG_PACK_PERM")) {
-            const int k = atoi(pe), n = (int)grid.y;
-            if (k > 1 && n > 2 * k) {
-                auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
-                perm = n / k;
-                while (gcd(perm, n) != 1) ++perm;
-            }
-        }
-        const bool burst = getenv("PG_PACK_BURST") == nullptr || atoi(getenv("PG_PACK_BURST")) != 0;       // (0: A/B runs, tests)
+        const int perm = pg_pack_perm(sw, (int)grid.y);
+        const bool burst = pg_pack3_burst(NP, sw);
         if (lanes <= 64 && burst) PG_PACK3B(64, 1);        // up to 512 slots (the north star: 400 haplotypes, 50 lanes)
-        else if (lanes <= 128 && burst) PG_PACK3B(128, 1);
+        else if (burst) PG_PACK3B(128, 1);
         else if (lanes <= 64) PG_PACK3(64);
         else if (lanes <= 128) PG_PACK3(128);
         else if (lanes <= 256) PG_PACK3(256);              // up to 2048 slots (C4: 2000 haplotypes): four waves meet in LDS per word
@@ -1049,7 +1040,7 @@ static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *g
         hipLaunchKernelGGL((k_pack2<64, DIP, 0>), grid, dim3(64), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
     else if (threads <= 128)
         hipLaunchKernelGGL((k_pack2<128, DIP, 0>), grid, dim3(128), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
-    else if (threads <= 256)
+    else if (route == PG_PACK_2)
         hipLaunchKernelGGL((k_pack2<256, DIP, 0>), grid, dim3(256), 0, st, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
     else {
         grid.z = (threads + 255) / 256;
@@ -1060,52 +1051,12 @@ static void launch_pack2(hipStream_t st, int threads, dim3 grid, const int8_t *g
 }
 
 // ---- the fused form: domain, tile tasks, launch ----
-// What it takes: called counts that k_pairC_big would form (up to 7 tiles of 32 units, matrix-core pairs) and rows that one wave
-// spans (up to 512 slots).  Where it pays: what it saves -- the plane's traffic and k_pairC_big's time -- grows with the units
-// (squared, for the products), what it costs -- eight waves coupled in one block that fills a CU -- does not, and a call of few
-// windows has to be cut into parts with atomics.  Measured per pass (profiles/r08): 200 units x 2000 windows of 50 kb 5.5 against
-// 6.15 ms; 100 units x 2000 windows of 5 kb 0.755 against 0.70; 100 units x 200 windows of 50 kb, six parts each, 0.77 against
-// 0.66.  So by itself the library takes it from 1024 windows a call and more than 128 units (five tiles) on; the unit bound lies
-// between the two measured unit counts and is not itself measured.  PG_PACK_FUSE=1 takes it anywhere in its domain (tests: parts
-// and atomics, small unit counts), PG_PACK_FUSE=0 keeps the two kernels (A/B runs, tests), and so does every switch that tunes
-// or selects them.
-bool pg_pack_fuse_fits(int NP, int NPv, int n_units, int n_win) {
-    const char *f = getenv("PG_PACK_FUSE");
-    if (f ? atoi(f) == 0 : (n_win < 1024 || n_units <= 128)) return false;
-    for (const char *e : {"PG_PAIR_VALU", "PG_PACK2", "PG_PACK_BURST", "PG_GROUP_WORDS", "PG_PACK_BLOCKS_PER_CU", "PG_OVERLAP", "PG_PACK_PERM"})
-        if (getenv(e)) return false;
-    return NP <= 512 && n_units >= 1 && pg_pair_big_fits(NPv, n_units);
-}
-
-// Tiles of the upper triangle of T x T dealt to the 8 waves, four products a[p] x b[p & 1] each: 2 x 2 blocks of tile rows
-// (2i, 2i+1) x tile columns (2j, 2j+1), j >= i -- six of them up to T = 6 --; at T = 7 the last tile column goes to two waves of its
-// own, rows 0 .. 3 and 4 .. 6 (28 tiles, 4 + 3 of them there).  Products outside the triangle run on cell 0 and are not stored.
-static void pg_fuse_tasks(int T, PgFuseArgs &fa) {
-    memset(fa.a, 0, sizeof fa.a);
-    memset(fa.b, 0, sizeof fa.b);
-    memset(fa.mask, 0, sizeof fa.mask);
-    const int Tb = T == 7 ? 6 : T;
-    int wv = 0;
-    for (int i = 0; i < Tb; i += 2)
-        for (int j = i; j < Tb; j += 2, ++wv)
-            for (int p = 0; p < 4; ++p) {
-                const int I = i + (p >> 1), J = j + (p & 1);
-                if (I < Tb && J < Tb && I <= J) {
-                    fa.a[wv][p] = (signed char)I;
-                    fa.b[wv][p & 1] = (signed char)J;
-                    fa.mask[wv] |= (unsigned char)(1u << p);
-                }
-            }
-    if (T == 7)
-        for (int i = 0; i < 7; i += 4, ++wv) {
-            fa.b[wv][0] = fa.b[wv][1] = 6;
-            for (int p = 0; p < 4 && i + p < 7; ++p) {
-                fa.a[wv][p] = (signed char)(i + p);
-                fa.mask[wv] |= (unsigned char)(1u << p);
-            }
-        }
-}
-
+// Where the library takes it is pg_pack_fuse_fits' decision, the tiles of its waves are pg_fuse_tasks' (pg_pair_plan.h).  Where it
+// pays: what it saves -- the plane's traffic and k_pairC_big's time -- grows with the units (squared, for the products), what it
+// costs -- eight waves coupled in one block that fills a CU -- does not, and a call of few windows has to be cut into parts with
+// atomics.  Measured per pass (profiles/r08): 200 units x 2000 windows of 50 kb 5.5 against 6.15 ms; 100 units x 2000 windows of 5 kb
+// 0.755 against 0.70; 100 units x 200 windows of 50 kb, six parts each, 0.77 against 0.66.  Hence 1024 windows and more than 128
+// units (five tiles); the unit bound lies between the two measured unit counts and is not itself measured.
 // nw[0 .. n_win): zeroed per-window word counters, as for pg_launch_pack2.  max_words / avg_words: words (32 sites) of the longest /
 // average window of the batch.
 int pg_launch_pack_fused(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi, const int64_t *goff,
@@ -1145,21 +1096,19 @@ int pg_launch_pack_fused(hipStream_t st, const int8_t *gt, int RS, const int64_t
     return 0;
 }
 
-// more slots than one k_pack3 block takes (or k_pack2 forced beyond one of ITS blocks): the presence pre-pass runs
-bool pg_pack_needs_presence(int NP) { return NP / 4 > 1024 || (getenv("PG_PACK2") != nullptr && NP / 4 > 256); }
-
 // pres: scratch of total_groups * PG_GROUP * 4 words, only used (and zeroed here) in that mode
 void pg_launch_pack2(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi,
                      const int64_t *goff, const int64_t *vgoff, int n_win, int max_groups, int64_t total_groups, uint32_t *Vp,
-                     int NPv, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch, uint32_t *pres, int capg, int grp) {
+                     int NPv, uint32_t *XV, int NP, int32_t *nw, int dip, int32_t *mismatch, uint32_t *pres, int capg, int grp,
+                     PgPackRoute route, const PgPairSwitches &sw) {
     // nw[0 .. n_win): the caller hands over zeroed per-window word counters (atomic allocation; k_pairD reads them even when
     // every window of the batch is empty); nw[n_win ..): one slot per group in the > 1024-slot mode (k_word_scan)
     if (n_win <= 0 || max_groups <= 0) return;
     const int threads = NP / 4;
-    if (pg_pack_needs_presence(NP)) (void)hipMemsetAsync(pres, 0, (size_t)total_groups * grp * 16u, st);
+    if (route == PG_PACK_2_PRESENCE) (void)hipMemsetAsync(pres, 0, (size_t)total_groups * grp * 16u, st);
     dim3 grid(max_groups, n_win);
-    if (dip) launch_pack2<1>(st, threads, grid, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
-    else launch_pack2<0>(st, threads, grid, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp);
+    if (dip) launch_pack2<1>(st, threads, grid, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp, route, sw);
+    else launch_pack2<0>(st, threads, grid, gt, RS, win_lo, win_hi, goff, vgoff, Vp, NPv, XV, NP, nw, mismatch, pres, capg, grp, route, sw);
 }
 
 // ------------------------------------------------------------------------------------------------------

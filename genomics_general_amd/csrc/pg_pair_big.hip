@@ -92,15 +92,7 @@ void launch(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, int n_win,
 
 }  // namespace
 
-// planes of up to 7 tiles of 32 units (the ring holds the T tile rows of a pair of groups, whatever the plane's stride); the
-// default form of the called counts at these sizes (PG_PAIR_TILE without a 'b' turns it off: pg_pair_tile.hip)
-bool pg_pair_big_fits(int NPv, int n_units) {
-    const char *sel = getenv("PG_PAIR_TILE");
-    if (sel && !strchr(sel, 'b')) return false;
-    const int T = (n_units + 31) / 32;
-    return T >= 1 && T <= 7 && NPv >= 32 * T;
-}
-
+// the default form of the called counts for planes of up to 7 tiles of 32 units (pg_pair_big_fits, pg_pair_plan.h)
 void pg_launch_pairC_big(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, int n_win, int NPv, int n_units, int diag,
                          int64_t avg_wq, int64_t max_sites, int32_t *Cmat) {
     if (n_win <= 0 || n_units <= 0) return;

@@ -37,8 +37,6 @@
 
 namespace {
 
-constexpr int NSTG = 3;                // ring depth (stages)
-
 // One LDS-DMA copy: 64 lanes x 16 bytes from each lane's `gsrc` to the wave-uniform LDS byte address `lds_dst` + 16 * lane.  Issued
 // from inline assembly on purpose: hipcc orders every ds_read behind ALL outstanding LDS-DMA it knows of (s_waitcnt vmcnt(0) in
 // front of the first fragment read), which would serialise the ring; these copies are invisible to its bookkeeping and are
@@ -393,23 +391,13 @@ int get_program(int T, int CS, int W, const int32_t **d_out, int *nblk_out) {
     return 0;
 }
 
-constexpr int CS_C = 4, W_C = 4, GP_C = 2;      // C: 4 waves x 4 slots, stage = 2 pairs of groups (512 sites)
+constexpr int CS_C = 4, W_C = 4;      // C: 4 waves x 4 slots, stage = PG_TILE_GP_C = 2 pairs of groups (512 sites)
 
 }  // namespace
 
-// The LDS-staged kernel takes planes of up to this many units per word (a stage must fit the ring).  PG_PAIR_TILE (A/B runs, tests)
-// chooses who counts the called pairs: a 'b' lets k_pairC_big (pg_pair_big.hip) take planes of up to 224 units, a 'c' lets
-// k_pairC_tile take what fits its ring, "none" leaves everything to the one-wave kernel of pg_pair_mfma.hip.  Default "bc".
+// Which planes the LDS-staged kernel takes (a stage must fit the ring), and PG_PAIR_TILE: pg_pair_tile_fits, pg_pair_plan.h.
 // (The LDS-staged form of the DIFFERENCE counts lost to the one-wave kernel on every shape -- 1.3 vs 0.85 ms on the north-star
 // shape -- and was removed in round 4; HISTORY.md.)
-bool pg_pair_tile_fits(int NPv) {
-    const char *sel = getenv("PG_PAIR_TILE");
-    if (!sel) sel = "bc";
-    if (!strchr(sel, 'c')) return false;
-    const int64_t stage = (int64_t)2 * GP_C * NPv * 16;
-    return NPv % 32 == 0 && stage * NSTG <= 64 * 1024;
-}
-
 int pg_launch_pairC_tile(hipStream_t st, const uint32_t *Vp, const int64_t *vgoff, int n_win, int NPv, int n_units, int diag,
                          int64_t avg_wq, int64_t max_sites, int32_t *Cmat) {
     if (n_win <= 0 || n_units <= 0) return 0;
@@ -420,7 +408,7 @@ int pg_launch_pairC_tile(hipStream_t st, const uint32_t *Vp, const int64_t *vgof
     const int kparts = std::max(pg_pick_parts(n_win, nblk * W_C, avg_wq / 2, 16, 4096), pg_exact_parts(max_sites));
     pg_zero_if_parts(st, Cmat, n_win, n_units, kparts);
     // ring shape: 2 pairs of groups per stage, 2 stages (measured on the north-star shape against 2 x 3 and 4 x 2: 1.24 / 1.31 / 1.28 ms)
-    constexpr int gp = 2, nst = 2;
+    constexpr int gp = PG_TILE_GP_C, nst = 2;
     const int stage_u4 = 2 * gp * NPv, chunks = stage_u4 / 64, nl = (chunks + W_C - 1) / W_C;
     const size_t lds_bytes = (size_t)nst * stage_u4 * 16;
     const int64_t blocks = pg_deal_blocks(n_win, (int64_t)nblk * kparts);

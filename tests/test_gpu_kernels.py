@@ -407,6 +407,56 @@ def test_every_pairwise_code_path_gives_the_same_integers(mode, monkeypatch):
     e.close()
 
 
+def _consecutive(lengths):
+    lo = np.cumsum([0] + list(lengths[:-1])).tolist()
+    return [(a, a + n) for a, n in zip(lo, lengths)]
+
+
+# a pass cut into sub-batches under a scratch limit of 64 MiB (csrc/pg_pair_plan.h): 200 diploids, 0.8 MB of matrices per window, about
+# 40 windows of 64 sites per half budget -- three batches through both plane slots, two empty windows and one of a single site --; and
+# 530 diploids, 5.6 MB per window, batches of five of the 12 windows of 0 .. 700 sites
+SEAM_SHAPES = {"200": (200, _consecutive([64] * 17 + [0] + [64] * 40 + [0] + [64] * 21 + [1] + [64] * 19), 2001),
+               "530": (530, _consecutive([0, 700, 33, 512, 1, 650, 700, 64, 300, 0, 699, 450]), 5301)}
+
+
+@pytest.fixture(scope="module")
+def seam_oracle():
+    """the oracle's counts of the windows of SEAM_SHAPES, computed once per shape"""
+    made = {}
+
+    def get(shape):
+        if shape not in made:
+            n_dip, wins, seed = SEAM_SHAPES[shape]
+            e, lay, codes, _ = G.make_engine(n_dip, 4, wins[-1][1], seed=seed)
+            e.close()
+            made[shape] = [orc.pair_counts_gemm(oracle_aln(lay, codes, a, b)) for a, b in wins]
+        return made[shape]
+    return get
+
+
+@pytest.mark.parametrize("shape,mode", [("200", "default"), ("200", "PG_PACK_FUSE=1"), ("200", "PG_NO_DIP"), ("200", "PG_PAIR_TILE=none"),
+                                        ("530", "default"), ("530", "PG_PACK2")])
+def test_sub_batches_under_a_scratch_limit_give_the_same_integers(shape, mode, seam_oracle, monkeypatch):
+    """the seams between sub-batches: batches alternating between the two plane slots, empty and one-site windows inside them, and
+    (530 diploids under PG_PACK2: the presence pre-pass) the per-group word counters behind the per-window ones in the staging vector;
+    the pack family's launch count shows that the pass really was cut"""
+    from genomics_general_amd import _lib
+    G.set_mode(monkeypatch, mode)
+    n_dip, wins, seed = SEAM_SHAPES[shape]
+    e, lay, codes, _ = G.make_engine(n_dip, 4, wins[-1][1], seed=seed)
+    e.set_scratch_limit(64 << 20)
+    e.kernel_time_select(None)
+    e.kernel_time_reset()
+    D, C = e.batch([w[0] for w in wins], [w[1] for w in wins]).pairCounts(reference_order=True)
+    launches = e.kernel_time(_lib.K_PACK)[1]
+    print("pack launches:", launches)
+    assert launches >= 3, launches
+    for k, (Do, Co) in enumerate(seam_oracle(shape)):
+        assert np.array_equal(C[k], Co), (shape, mode, "C", k)
+        assert np.array_equal(D[k], Do), (shape, mode, "D", k)
+    e.close()
+
+
 DEAL_WINS = [(a, a + n) for a, n in zip(np.cumsum([0] + [64, 1500] * 9).tolist(), [64, 1500] * 9 + [64])]      # 19 consecutive windows
 
 

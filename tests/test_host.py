@@ -658,3 +658,21 @@ def test_the_pair_kernels_block_dealing_walked_as_a_program_of_its_own(tmp_path)
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 0, (r.returncode, r.stdout.decode()[-2000:], r.stderr.decode()[-3000:])
     assert r.stdout.decode().strip() == "%d cases, 0 bad" % (41 * 7)
+
+
+def test_the_pair_pass_plan_walked_as_a_program_of_its_own(tmp_path):
+    """tests/pair_plan_main.cpp: csrc/pg_pair_plan.h's switches, predicates, routes, batch cuts and staging layouts over a grid that
+    straddles every boundary in them, under AddressSanitizer and UndefinedBehaviorSanitizer: every decision is the one recorded from
+    the commit before the plan was lifted out of pairwise_batches (tests/golden/pair_plan/parent_decisions.txt), the batches tile
+    the windows within their limits, the staging regions do not overlap, pg_fuse_tasks covers the upper triangle once"""
+    import subprocess
+    exe = str(tmp_path / "pair_plan_main")
+    table = os.path.join(ROOT, "tests", "golden", "pair_plan", "parent_decisions.txt")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "pair_plan_main.cpp"), "-o", exe])
+    env = {k: v for k, v in os.environ.items() if not k.startswith("PG_")}       # (the program sets the switch of each case itself)
+    r = subprocess.run([exe, table], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    assert r.returncode == 0, (r.returncode, r.stdout.decode()[-2000:], r.stderr.decode()[-3000:])
+    with open(table) as f:
+        n_cases = sum(1 for line in f) - 1
+    assert n_cases == 732 and r.stdout.decode().strip() == "%d cases, 0 bad" % n_cases
