@@ -126,6 +126,19 @@ SIGNATURES = {
     "pg_filter_dev_rows_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
     "pg_filter_dev_text": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
     "pg_filter_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_seq_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]),
+    "pg_seq_free": (None, [C.c_void_p]),
+    "pg_seq_dev_config": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "pg_seq_dev_submit": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int64]),
+    "pg_seq_dev_submit_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_char_p, C.c_int64, C.c_int64]),
+    "pg_seq_dev_parse": (C.c_int, [_P, C.c_int]),
+    "pg_seq_dev_collect": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_seq_dev_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64]),
+    "pg_seq_dev_meta": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_seq_dev_text": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "pg_seq_dev_timing": (C.c_int, [_P, C.c_int]),
+    "pg_seq_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pg_format_freq_rows": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, _i64p, _i32p, C.c_char_p, _i64p, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.POINTER(C.c_int64), C.c_int]),
     "pg_inflate_chunks": (C.c_int, [C.c_void_p, _i64p, _i64p, _i64p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),

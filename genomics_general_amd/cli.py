@@ -2049,3 +2049,14 @@ def distpaint_main(argv=None):
     run.report_timing()
     run.finish()
     return 0
+
+
+# ==========================================================================================================
+# genoToSeq.py  (.geno windows as fasta / phylip alignments; genomics_general_amd/genoseq.py)
+# ==========================================================================================================
+@guarded_main
+def genotoseq_main(argv=None):
+    """Drop-in for the reference's genoToSeq.py (genoToSeq.py:35-123): the sites' characters are transposed into sequences by
+    k_seq_lines / k_seq_tile"""
+    from . import genoseq
+    return genoseq.main(argv)

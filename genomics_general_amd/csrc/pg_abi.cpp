@@ -217,6 +217,14 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
         F.flags.release(); F.out.release(); F.rlen.release(); F.roff.release(); F.pos.release(); F.status.release(); F.h_status.release(); F.df.release();
         if (F.done) (void)hipEventDestroy(F.done);
     }
+    c->seq.sel_col.release(); c->seq.sel_off.release(); c->seq.sel_len.release();
+    for (int k = 0; k < 2; ++k) {
+        pg_ctx::SeqDev::Slot &Q = c->seq.s[k];
+        Q.keep.release(); Q.runf.release(); Q.rrun.release(); Q.out.release(); Q.row.release(); Q.pos.release(); Q.rpos.release(); Q.rstart.release();
+        Q.line_of.release(); Q.status.release(); Q.h_status.release();
+        for (hipEvent_t e : {Q.done, Q.t0, Q.t1, Q.t2, Q.t3})
+            if (e) (void)hipEventDestroy(e);
+    }
     c->tok_pin.release();
     drop_events(c);
     c->gt.release();

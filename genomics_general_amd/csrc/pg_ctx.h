@@ -211,6 +211,27 @@ struct pg_ctx {
         bool bgzf_rows = false;
         int64_t blocks = 0, host_blocks = 0;
     } filt;
+    // .geno lines turned into sequences on the device (pg_seq_dev.hip): the option set, the selection tables and, per text slot of the
+    // tokenizer, the lines' records, the kept lines' places, the sites' records and the matrix [n_seq][pitch]
+    struct SeqDev {
+        bool configured = false;
+        pg_seq_cfg cfg;
+        int tile_seqs = 0;                                 // output sequences per tile of k_seq_tile
+        DevBuf<int32_t> sel_col, sel_off, sel_len;
+        struct Slot {
+            DevBuf<uint32_t> keep;                         // per line: 1 a site, 0 a '#' line
+            DevBuf<uint8_t> runf, rrun, out;               // runf / rrun: the scaffold differs from the site before, per line / per site
+            DevBuf<int64_t> row, pos, rpos, rstart, line_of, status;   // status: [0] bits (1 a line needs the host), [1] first such line, [3] sites
+            HostPin<int64_t> h_status;
+            int64_t n_lines = 0, text_len = 0, pitch = 0;
+            hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
+            int state = 0;                                 // 0 idle, 1 text there, 2 kernels queued, 3 empty block
+            bool no_final_newline = false, timed = false;
+        } s[2];
+        bool timing = false;
+        double lines_ms = 0, tile_ms = 0;
+        int64_t blocks = 0, host_blocks = 0;
+    } seq;
     int64_t tok_nl_fallbacks = 0;                          // deflated blocks whose line feeds were found by passes over the text after all
     HostPin<uint8_t> tok_pin;                              // two 4 MiB page-locked buffers per staging thread
     hipStream_t tok_st[PG_TOK_WORKERS] = {};               // one copy stream per staging thread

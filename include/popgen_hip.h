@@ -674,6 +674,74 @@ int pg_filter_dev_rows_bgzf(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
 int pg_filter_dev_text(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
 int pg_filter_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
 
+/* ---- `.geno` lines turned into sequences (the genoToSeq.py drop-in, genomics_general_amd/genoseq.py) -----------------------------
+ * Replaces the per-site loop of genoToSeq.py: parseGenoLine (genomics.py:1884-1902), GenoWindow.addSite / seqDict (1753-1793) and the
+ * join of makeAlnString (2232-2251) -- a byte transpose, site-major text in, sequence-major bytes out.  The per-line and per-cell rules
+ * are csrc/pg_seq_core.h.  The option set: */
+typedef struct pg_seq_cfg {
+    int32_t n_cols;                                          /* fields of the header line */
+    int32_t n_seq;                                           /* output sequences */
+    int32_t split;                                           /* --splitPhased: a sequence is one character of a cell */
+    int32_t n_to_gap;                                        /* --NtoGap */
+    int32_t exact_cols;                                      /* every column is taken (no -S): a line with more fields than the header
+                                                                stops the run too */
+} pg_seq_cfg;
+/* The tables beside it, one entry per output sequence: sel_col the file column (2 ..), sel_off the character's offset within the cell
+ * (0 when the cell is copied whole), sel_len the length the cell must have (2 * ploidy - 1 under --splitPhased; 0: any, copied whole).
+ *
+ * What a block of lines gives: */
+typedef struct pg_seq_block {
+    int64_t n_sites, n_runs;
+    int64_t stride;                                          /* > 0: every sequence has `stride` bytes per site, sequence q lies at
+                                                                seq + q * n_sites * stride; 0: see off */
+    int64_t seq_bytes;
+    uint8_t *seq;                                            /* the sequences' bytes, one sequence after the other */
+    int64_t *off;                                            /* stride == 0: [n_seq][n_sites + 1] places in seq (site i of sequence q:
+                                                                off[q * (n_sites + 1) + i] up to the entry behind it) */
+    int64_t *pos;                                            /* [n_sites] */
+    int64_t *run_start;                                      /* [n_runs] first site of every scaffold run of the block */
+    int64_t *run_name;                                       /* [n_runs][2] where the run's scaffold stands in text: offset, length */
+    int64_t err_line;                                        /* -1, or the block's line (0-based, '#' lines counted) the reference dies on; */
+    int32_t err_code;                                        /*   why: PGS_E_* (pg_seq_core.h).  The sites in front of it are complete */
+} pg_seq_block;
+/* Host route, every spelling line.split() takes: text[0 .. len) holds whole lines (the last may lack its line feed), lines that begin
+ * with '#' are skipped.  Free the block's arrays with pg_seq_free. */
+int pg_seq_text(const pg_seq_cfg *cfg, const int32_t *sel_col, const int32_t *sel_off, const int32_t *sel_len, const char *text, int64_t len,
+                pg_seq_block *out);
+void pg_seq_free(pg_seq_block *block);
+/* Device route (csrc/pg_seq_dev.hip) for the regular spelling (fields split by single tabs, the header's field count, ASCII, selected
+ * cells of 2 * ploidy - 1 characters under --splitPhased and of one character otherwise), two slots in flight:
+ *   pg_seq_dev_config       the option set; tile_seqs: output sequences per tile of k_seq_tile (0: as many as the LDS holds);
+ *                           *taken_out = 0 when the device does not take it (a header too wide for the tab tables in LDS)
+ *   pg_seq_dev_submit       a block of whole lines -> the tokenizer's text slot `slot` (0 / 1), its line feeds listed there
+ *   pg_seq_dev_submit_bgzf  the same for a block still deflated (bgzip's members, pg_bgzf_walk's table; head: text in front of them):
+ *                           the members cross PCIe deflated and k_inflate writes their text into the slot
+ *   pg_seq_dev_parse        queues k_seq_lines, the scan of the kept lines, k_seq_rows and k_seq_tile
+ *   pg_seq_dev_collect      waits.  *host_line_out < 0: the matrix [n_seq][*n_sites_out] is ready for pg_seq_dev_rows, the sites'
+ *                           positions, run flags (1: the scaffold differs from the site before; the block's first site always) and
+ *                           line starts for pg_seq_dev_meta; else line *host_line_out of the block is one the device does not take: the
+ *                           block goes to pg_seq_text (pg_seq_dev_text brings its text back).  *n_lines_out: the block's line feeds,
+ *                           *pitch_out: bytes between two sequences of the matrix on the device
+ *   pg_seq_dev_rows         sequences q0 .. q1 - 1 of the matrix, `width` bytes of each (up to the pitch), -> dst with dst_pitch bytes
+ *                           between them (page-locked memory makes it one DMA)
+ *   pg_seq_dev_meta         pos_dst[n_sites], run_dst[n_sites], start_dst[n_sites] (where each site's line begins in the text)
+ *   pg_seq_dev_text         len bytes of the collected block's text from offset off
+ *   pg_seq_dev_stats        blocks transposed on the device / handed to the host so far; milliseconds of k_seq_lines and of k_seq_tile
+ *                           (HIP events, only under pg_seq_dev_timing(ctx, 1): the events make collect wait for each kernel) */
+int pg_seq_dev_config(pg_ctx *ctx, const pg_seq_cfg *cfg, const int32_t *sel_col, const int32_t *sel_off, const int32_t *sel_len,
+                      int tile_seqs, int *taken_out);
+int pg_seq_dev_submit(pg_ctx *ctx, int slot, const char *text, int64_t len);
+int pg_seq_dev_submit_bgzf(pg_ctx *ctx, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                           const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                           int64_t text_len);
+int pg_seq_dev_parse(pg_ctx *ctx, int slot);
+int pg_seq_dev_collect(pg_ctx *ctx, int slot, int64_t *n_sites_out, int64_t *host_line_out, int64_t *n_lines_out, int64_t *pitch_out);
+int pg_seq_dev_rows(pg_ctx *ctx, int slot, int q0, int q1, uint8_t *dst, int64_t dst_pitch, int64_t width);
+int pg_seq_dev_meta(pg_ctx *ctx, int slot, int64_t *pos_dst, uint8_t *run_dst, int64_t *start_dst);
+int pg_seq_dev_text(pg_ctx *ctx, int slot, int64_t off, int64_t len, uint8_t *dst);
+int pg_seq_dev_timing(pg_ctx *ctx, int on);
+int pg_seq_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out, double *lines_ms_out, double *tile_ms_out);
+
 #ifdef __cplusplus
 }
 #endif
