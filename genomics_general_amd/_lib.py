@@ -139,6 +139,23 @@ SIGNATURES = {
     "pg_seq_dev_text": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
     "pg_seq_dev_timing": (C.c_int, [_P, C.c_int]),
     "pg_seq_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pg_merge_text": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "pg_merge_free": (None, [C.c_void_p]),
+    "pg_merge_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),
+    "pg_merge_dev_config": (C.c_int, [_P, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "pg_merge_dev_submit": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int64]),
+    "pg_merge_dev_submit_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_char_p, C.c_int64, C.c_int64]),
+    "pg_merge_dev_keys": (C.c_int, [_P, C.c_void_p]),
+    "pg_merge_dev_set_output": (C.c_int, [_P, C.c_int]),
+    "pg_merge_dev_merge": (C.c_int, [_P, C.c_int, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64)]),
+    "pg_merge_dev_rows": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
+    "pg_merge_dev_advance": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_merge_dev_text": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
+    "pg_merge_dev_timing": (C.c_int, [_P, C.c_int]),
+    "pg_merge_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pg_merge_dev_end": (C.c_int, [_P]),
     "pg_format_freq_rows": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_void_p, _i64p, _i32p, C.c_char_p, _i64p, C.c_void_p, C.c_void_p,
                                       C.c_int64, C.POINTER(C.c_int64), C.c_int]),
     "pg_inflate_chunks": (C.c_int, [C.c_void_p, _i64p, _i64p, _i64p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),

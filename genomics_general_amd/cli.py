@@ -2060,3 +2060,14 @@ def genotoseq_main(argv=None):
     k_seq_lines / k_seq_tile"""
     from . import genoseq
     return genoseq.main(argv)
+
+
+# ==========================================================================================================
+# mergeGeno.py  (SURVEY.md section 2 row 15: .geno files joined by site; genomics_general_amd/mergegeno.py)
+# ==========================================================================================================
+@guarded_main
+def mergegeno_main(argv=None):
+    """Drop-in for the reference's mergeGeno.py (mergeGeno.py:11-88): the files' lines are keyed, matched and copied by libpopgen_hip.so
+    (pg_merge_dev_*: the device route; pg_merge_text: the host route)."""
+    from . import mergegeno
+    return mergegeno.main(argv)

@@ -159,6 +159,7 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
     (void)hipStreamSynchronize(c->stream_up);
     pg_comm_destroy(c);
     (void)pg_sfs_end(c);
+    (void)pg_merge_dev_end(c);
     c->paint.release();
     for (int k = 0; k < 2; ++k) {
         c->slot[k].Vp.release();

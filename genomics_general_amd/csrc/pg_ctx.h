@@ -267,6 +267,7 @@ struct pg_ctx {
         void release() { tab.release(); out.release(); crit.release(); count.release(); cell.release(); means.release(); }
     } paint;
     void *sfs = nullptr;           // pg_sfs_begin .. pg_sfs_end: the spectra's tables and staging (pg_sfs.hip owns the type)
+    void *merge = nullptr;         // pg_merge_dev_config .. pg_merge_dev_end: the files' text regions, keys and the round's output (pg_merge_dev.hip owns the type)
     // pi / dxy / Fst in NumPy's summation order (k_popdist_np): the reference's row order within the populations and the rank of
     // the population names (pg_set_reference_order; identity until set), the pairwise-summation trees of the block lengths
     DevBuf<int32_t> ref_row, pop_rank, np_trees, np_task_tree;

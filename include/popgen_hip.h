@@ -742,6 +742,91 @@ int pg_seq_dev_text(pg_ctx *ctx, int slot, int64_t off, int64_t len, uint8_t *ds
 int pg_seq_dev_timing(pg_ctx *ctx, int on);
 int pg_seq_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out, double *lines_ms_out, double *tile_ms_out);
 
+/* ---- `.geno` files joined by site (the mergeGeno.py drop-in, genomics_general_amd/mergegeno.py) ------------------------------------
+ * Replaces the walk of mergeGeno.py:57-88 over every position of every scaffold of the .fai: a sorted join of text files.  A site is
+ * (line of the scaffold in the .fai, position); a file gives the longest prefix of its lines whose sites are valid and increasing
+ * (the first other line stops it).  The per-line rules are csrc/pg_merge_core.h, the planning of the rounds csrc/pg_merge_plan.h.
+ * The option set: */
+typedef struct pg_merge_cfg {
+    int32_t n_files;                                         /* 1 .. 32 */
+    int32_t method;                                          /* 0 intersect, 1 union, 2 all */
+    int32_t union_min;                                       /* max(--unionMin, --mustIncludeFirst) */
+    int32_t must_first;                                      /* --mustIncludeFirst */
+    uint32_t out_mask;                                       /* bit f: the cells of file f are written (--outputOnly) */
+    int32_t sep_len, missing_len;                            /* bytes of --outSep and of --missing */
+    int32_t n_fai;                                           /* scaffolds of the .fai */
+} pg_merge_cfg;
+/* The .fai beside it: the names side by side in fai_names, name f at name_off[f] .. name_off[f + 1], and the lengths.
+ *
+ * One input file of a round of the host route: */
+typedef struct pg_merge_input {
+    const char *text;                                        /* its resident lines (whole lines; the last may lack its line feed when */
+    int64_t len;                                             /*   nothing follows) */
+    int32_t open;                                            /* 1: the input goes on behind them */
+    int32_t n_cols;                                          /* fields of its header */
+    int32_t prev_scaf;                                       /* in: the key of the last line the rounds before consumed (scaffold -1: */
+    int64_t prev_pos;                                        /*   none); out: of the last line consumed so far */
+    int32_t stop;                                            /* out: PGM_STOP_* when a line of this block stops the file */
+    int64_t stop_line;                                       /*   that line (0-based in the block) */
+    int64_t lines_done, bytes_done;                          /* out: lines and bytes of the block at or below the horizon */
+} pg_merge_input;
+typedef struct pg_merge_result {
+    char *out;                                               /* the written lines */
+    int64_t out_len, rows;
+    int32_t from_scaf, hor_scaf;                             /* in: the horizon of the round before ({0, 0} at the start); out: this */
+    int64_t from_pos, hor_pos;                               /*   round's horizon */
+    int32_t last;                                            /* nothing is left behind this round */
+    int32_t stalled;                                         /* an open file held no consumable line: nothing was written, read it further */
+    int32_t err_code, err_file;                              /* PGM_E_* (pg_merge_core.h): the input is rejected; which file, */
+    int64_t err_line;                                        /*   which line of its block */
+} pg_merge_result;
+/* Host route, every spelling line.split() takes: one round over the files' resident lines (its horizon planned by pg_merge_plan.h from
+ * the keys found here; out_cap: the output budget of a round of the methods that write sites no file holds -- bytes of
+ * lines no file adds to; the resident input does not come off it).  Free res->out with pg_merge_free. */
+int pg_merge_text(const pg_merge_cfg *cfg, const char *sep, const char *missing, const char *fai_names, const int64_t *name_off,
+                  const int64_t *fai_len, pg_merge_input *files, int64_t out_cap, pg_merge_result *res);
+void pg_merge_free(pg_merge_result *res);
+/* The plan of a round of the device route (pg_merge_plan.h), from pg_merge_dev_keys' info and from whether each file's input goes on.
+ * round: [0] [1] where the round begins, [2] [3] its horizon, [4] stalled, [5] last, [6] the candidates are positions (dense) */
+int pg_merge_plan(const pg_merge_cfg *cfg, const int64_t *fai_len, const int32_t *n_cols, int64_t max_name, const int64_t *info,
+                  const int32_t *open, int64_t out_cap, int32_t from_scaf, int64_t from_pos, int64_t *round);
+/* Device route (csrc/pg_merge_dev.hip) for the regular spelling (fields split by single tabs, no other ASCII whitespace, the header's
+ * field count, ASCII, a final line feed) and a one-byte separator.  Every file owns a text region on the device; a round:
+ *   pg_merge_dev_config       the option set, the .fai, per file the fields of its header; *taken_out = 0 when the device does not
+ *                             take it (a separator that is not one byte, --missing beyond 64 bytes, a header of fewer than two fields)
+ *   pg_merge_dev_submit       a block of whole lines of file f, behind the lines the rounds before left in its region
+ *   pg_merge_dev_submit_bgzf  the same for a block still deflated (bgzip's members, pg_bgzf_walk's table; head: text in front of
+ *                             them): k_inflate writes the text, with its line feeds listed
+ *   pg_merge_dev_keys         k_merge_keys over the new lines and the scan for the stopping line.  Per file, info[f * 8 ..]: [0] lines
+ *                             resident, [1] consumable lines among them, [2] the last one's scaffold, [3] its position, [4] PGM_STOP_*
+ *                             when a line stops the file, [5] that line (counted in the region), [6] 1: a line outside the regular
+ *                             spelling at or in front of it (the round is pg_merge_text's), [7] bytes resident (what the rounds consumed not counted)
+ *   pg_merge_dev_merge        the round behind (from_scaf, from_pos) up to the horizon: k_merge_lines or k_merge_pos, the scan of the lines' lengths,
+ *                             k_merge_emit, and -- pg_merge_dev_set_output(ctx, 1) -- k_deflate over the lines.  dense: the candidates
+ *                             are the positions of the range (one scaffold), else the lines of the files.  done[f * 4 ..]: lines and
+ *                             bytes of file f the round consumed, the key of its last line consumed so far; *bytes_out, *rows_out, *bgzf_out: what pg_merge_dev_rows brings
+ *   pg_merge_dev_rows         the written lines (bgzf = 0) or their BGZF members (bgzf = 1)
+ *   pg_merge_dev_advance      after a round of the host route: the lines and bytes it consumed per file (done[f * 2 ..]), the keys it ended on
+ *   pg_merge_dev_text         the resident text of file f (for pg_merge_text; a deflated block's text never was on the host)
+ *   pg_merge_dev_stats        rounds merged on the device; milliseconds of k_merge_keys, of k_merge_lines / k_merge_pos and of k_merge_emit (HIP events,
+ *                             only under pg_merge_dev_timing(ctx, 1)) */
+int pg_merge_dev_config(pg_ctx *ctx, const pg_merge_cfg *cfg, const char *sep, const char *missing, const char *fai_names,
+                        const int64_t *name_off, const int64_t *fai_len, const int32_t *n_cols, int *taken_out);
+int pg_merge_dev_submit(pg_ctx *ctx, int f, const char *text, int64_t len);
+int pg_merge_dev_submit_bgzf(pg_ctx *ctx, int f, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                             const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                             int64_t text_len);
+int pg_merge_dev_keys(pg_ctx *ctx, int64_t *info);
+int pg_merge_dev_set_output(pg_ctx *ctx, int bgzf);
+int pg_merge_dev_merge(pg_ctx *ctx, int dense, int32_t from_scaf, int64_t from_pos, int32_t hor_scaf, int64_t hor_pos, int64_t *done,
+                       int64_t *bytes_out, int64_t *rows_out, int64_t *bgzf_out);
+int pg_merge_dev_rows(pg_ctx *ctx, int bgzf, uint8_t *dst, int64_t len);
+int pg_merge_dev_advance(pg_ctx *ctx, const int64_t *done, const int32_t *prev_scaf, const int64_t *prev_pos);
+int pg_merge_dev_text(pg_ctx *ctx, int f, uint8_t *dst, int64_t len);
+int pg_merge_dev_timing(pg_ctx *ctx, int on);
+int pg_merge_dev_stats(pg_ctx *ctx, int64_t *rounds_out, double *keys_ms_out, double *match_ms_out, double *emit_ms_out);
+int pg_merge_dev_end(pg_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif
