@@ -10,6 +10,7 @@
 //   k_tok_parse                           one wave per line: lane 0 reads scaffold + position, the lanes take the cells
 //                                         c, c+64, ... -> one-hot codes written into the row at the slots of the layout
 #include "pg_ctx.h"
+#include "pg_tok_plan.h"
 #include "pg_wave.h"
 
 #include <algorithm>
@@ -977,12 +978,14 @@ static int tok_parse(pg_ctx *c, int slot, int64_t row_offset, int64_t row_capaci
     if ((rc = T.pos64.ensure_roomy((size_t)n_lines + 8)) != PG_OK) return rc;                       // positions (int64)
     if ((rc = T.off.ensure((size_t)run_cap * 2)) != PG_OK) return rc;                         // run_row, run_off
     if ((rc = T.h_pos.ensure_roomy((size_t)n_lines)) != PG_OK) return rc;
-    // the form with several lines per wavefront, the column tables and the row being put together in LDS (k_tok_parse2) whenever they
-    // fit; PG_TOK_PARSE=1: the first form (one line per wavefront, tables in global memory, rows cleared first), which is also the
-    // route of wider layouts
-    const size_t tab_bytes = (size_t)n_cols * (max_ploidy + 3) * 4, lds_bytes = tab_bytes + 4 * (size_t)c->S;
-    static const bool first_form = getenv("PG_TOK_PARSE") && atoi(getenv("PG_TOK_PARSE")) == 1;
-    const bool second_form = lds_bytes <= 60 * 1024 && !first_form;
+    // the form with several lines per wavefront, the column tables and the row being put together in LDS (k_tok_heads + a cell
+    // kernel) whenever they fit; PG_TOK_PARSE=1: the first form (one line per wavefront, tables in global memory, rows cleared first),
+    // which is also the route of wider layouts.  pg_plan_tok (pg_tok_plan.h) decides; the switches are read once per process
+    static const PgTokSwitches tok_sw = pg_tok_switches();
+    int widest = 0;
+    for (int k = 0; k < n_cols; ++k) widest = std::max(widest, (int)T.cols[(size_t)n_cols * (max_ploidy + 2) + k]);
+    const PgTokPlan plan = pg_plan_tok(n_cols, max_ploidy, c->S, widest, tok_sw);
+    const bool second_form = plan.route != PG_TOK_ROUTE_PARSE;
     // (the first form scatters int8 slots straight to global memory: into a cleared int8 block of its own, which k_nib_pack then
     // turns into resident rows -- no two lanes ever share a byte of a resident row)
     if (!second_form) {
@@ -1017,22 +1020,16 @@ static int tok_parse(pg_ctx *c, int slot, int64_t row_offset, int64_t row_capaci
         }
         const int64_t per_block = 4 * TOK_LPW;
         const dim3 grid((unsigned)((n_lines + per_block - 1) / per_block));
-        int widest = 0;
-        for (int k = 0; k < n_cols; ++k) widest = std::max(widest, (int)T.cols[(size_t)n_cols * (max_ploidy + 2) + k]);
-        const size_t lds3 = (size_t)n_cols * 16 + 256 + 4 * ((size_t)c->S + 64);
-        static const bool general_cells = getenv("PG_TOK_PARSE") && atoi(getenv("PG_TOK_PARSE")) == 2;      // (A/B, tests)
-        if (widest <= 3 && lds3 <= 60 * 1024 && !general_cells) {
-#define PG_CELLS3N(F, N) hipLaunchKernelGGL((k_tok_cells3<F, N>), grid, dim3(256), lds3, st, T.tp, T.cells_at.p, n_lines, n_cols, max_ploidy, T.dcols.p, \
+        if (plan.route == PG_TOK_ROUTE_CELLS3) {
+#define PG_CELLS3N(F, N) hipLaunchKernelGGL((k_tok_cells3<F, N>), grid, dim3(256), plan.lds_bytes, st, T.tp, T.cells_at.p, n_lines, n_cols, max_ploidy, T.dcols.p, \
                                             c->gt.p + row_offset * c->RS, c->S, d_status, dip)
             // (a lane's column-table entries in registers for layouts of up to 256 columns; PG_TOK_CELLS_REGS=0: the table read per step)
-            static const bool in_regs = !(getenv("PG_TOK_CELLS_REGS") && atoi(getenv("PG_TOK_CELLS_REGS")) == 0);
-            const int nit = (n_cols + 63) / 64;
 #define PG_CELLS3(F)                                         \
     do {                                                     \
-        if (!in_regs || nit > 4) PG_CELLS3N(F, 0);           \
-        else if (nit == 1) PG_CELLS3N(F, 1);                 \
-        else if (nit == 2) PG_CELLS3N(F, 2);                 \
-        else if (nit == 3) PG_CELLS3N(F, 3);                 \
+        if (plan.nit == 0) PG_CELLS3N(F, 0);                 \
+        else if (plan.nit == 1) PG_CELLS3N(F, 1);            \
+        else if (plan.nit == 2) PG_CELLS3N(F, 2);            \
+        else if (plan.nit == 3) PG_CELLS3N(F, 3);            \
         else PG_CELLS3N(F, 4);                               \
     } while (0)
             if (T.fmt == PG_FMT_DIPLO) PG_CELLS3(PG_FMT_DIPLO);
@@ -1041,7 +1038,7 @@ static int tok_parse(pg_ctx *c, int slot, int64_t row_offset, int64_t row_capaci
 #undef PG_CELLS3
 #undef PG_CELLS3N
         } else {
-            hipLaunchKernelGGL(k_tok_cells, grid, dim3(256), lds_bytes, st, T.tp, T.cells_at.p,
+            hipLaunchKernelGGL(k_tok_cells, grid, dim3(256), plan.lds_bytes, st, T.tp, T.cells_at.p,
                                n_lines, T.fmt, n_cols, max_ploidy, T.dcols.p, c->gt.p + row_offset * c->RS, c->S, d_status, dip);
         }
     } else {

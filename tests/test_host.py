@@ -676,3 +676,130 @@ def test_the_pair_pass_plan_walked_as_a_program_of_its_own(tmp_path):
     with open(table) as f:
         n_cases = sum(1 for line in f) - 1
     assert n_cases == 732 and r.stdout.decode().strip() == "%d cases, 0 bad" % n_cases
+
+
+# ---- the device tokenizer's case table (tests/tok_cases.py) and its route plan (csrc/pg_tok_plan.h), without a GPU ----------------------
+import functools  # noqa: E402
+
+import tok_cases as TC  # noqa: E402
+
+
+@functools.lru_cache(maxsize=None)
+def tok_table():
+    return [TC.build(sp) for sp in TC.regular()]
+
+
+def _tok_kernel(case, route, nit):
+    fmt = {"diplo": "DIPLO", "phased": "PHASED"}.get(case.spec.fmt, "PAIRS")              # (pairs and haplo: an allele per character)
+    return {"PARSE": "k_tok_parse", "CELLS": "k_tok_cells"}.get(route) or "k_tok_cells3<%s, %d>" % (fmt, nit)
+
+
+def test_the_tokenizer_plan_walked_as_a_program_of_its_own(tmp_path):
+    """tests/tok_plan_main.cpp: csrc/pg_tok_plan.h's pg_plan_tok over the shapes of the case table, under AddressSanitizer and
+    UndefinedBehaviorSanitizer.  The table reaches every route: the fifteen k_tok_cells3<DIPLO | PHASED | PAIRS, 0 .. 4>, k_tok_cells
+    by a wide wanted cell, by a wide unwanted column and by k_tok_cells3's LDS size, k_tok_parse by size; under PG_TOK_PARSE=1 every
+    case takes k_tok_parse, under PG_TOK_PARSE=2 every case of the second form k_tok_cells, under PG_TOK_CELLS_REGS=0 k_tok_cells3
+    reads its table per step.  A few plans are held against the figures worked out by hand from the kernels' LDS layouts"""
+    import subprocess
+    exe = str(tmp_path / "tok_plan_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "tok_plan_main.cpp"), "-o", exe])
+    # by hand: k_tok_cells3 asks for 16 n_cols + 256 + 4 (S + 64) bytes, k_tok_cells for 4 n_cols (max_ploidy + 3) + 4 S
+    hand = {(200, 2, 400, 3): ("CELLS3", 4, 5312), (64, 1, 64, 1): ("CELLS3", 1, 1792), (65, 2, 144, 3): ("CELLS3", 2, 2128),
+            (192, 2, 384, 1): ("CELLS3", 3, 5120), (256, 3, 768, 3): ("CELLS3", 4, 7680), (257, 2, 528, 3): ("CELLS3", 0, 6736),
+            (3, 26, 32, 51): ("CELLS", 0, 476), (10, 2, 32, 7): ("CELLS", 0, 328), (2193, 2, 4400, 3): ("PARSE", 0, 0),
+            (2192, 2, 4384, 3): ("CELLS3", 0, 53120), (3045, 1, 3056, 1): ("CELLS", 0, 60944), (3044, 1, 3056, 1): ("CELLS3", 0, 61440)}
+    assert dict(zip(hand, TC.plan(list(hand), exe=exe))) == hand
+    r = subprocess.run([exe, "0:1:16:1"], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 1 and b"bad shape" in r.stderr
+    table = tok_table()
+    shapes = [TC.shape_of(c) for c in table]
+    default = TC.plan(shapes, exe=exe)
+    reached = {}
+    for c, (route, nit, lds) in zip(table, default):
+        reached.setdefault(_tok_kernel(c, route, nit), []).append(c)
+    want = {"k_tok_cells3<%s, %d>" % (f, n) for f in ("DIPLO", "PHASED", "PAIRS") for n in range(5)} | {"k_tok_cells", "k_tok_parse"}
+    assert set(reached) == want, sorted(want ^ set(reached))
+    print("\n".join("%-28s %4d cases, e.g. %s" % (k, len(v), v[0].name) for k, v in sorted(reached.items())))
+    why = {"wide wanted cell": 0, "wide unwanted column": 0, "LDS size": 0}
+    for c in reached["k_tok_cells"]:
+        wanted_widest = int(c.width[c.wanted_col].max())
+        why["wide wanted cell" if wanted_widest > 3 else "wide unwanted column" if c.widest > 3 else "LDS size"] += 1
+    assert all(why.values()), why
+    assert all(c.widest <= 3 for c in reached["k_tok_parse"])                                  # by size, not by a switch
+    first_cells, last_second, first_parse = TC.size_edges()
+    assert (first_cells, last_second, first_parse) == (3045, 2192, 2193)                      # (where the LDS formulas above put them)
+    # the switch-forced routes
+    for switches, rule in (({"PG_TOK_PARSE": "1"}, lambda d: ("PARSE", 0, 0)),
+                           ({"PG_TOK_PARSE": "2"}, lambda d: d if d[0] == "PARSE" else ("CELLS", 0, None)),
+                           ({"PG_TOK_CELLS_REGS": "0"}, lambda d: (d[0], 0, d[2])),
+                           ({"PG_TOK_PARSE": "0", "PG_TOK_CELLS_REGS": "1"}, lambda d: d),
+                           ({"PG_TOK_PARSE": "3"}, lambda d: d)):
+        forced = TC.plan(shapes, switches, exe=exe)
+        kernels = {}
+        for c, d, f in zip(table, default, forced):
+            w = rule(d)
+            assert f[:2] == w[:2] and (w[2] is None or f[2] == w[2]), (switches, c.name, d, f)
+            kernels[_tok_kernel(c, f[0], f[1])] = kernels.get(_tok_kernel(c, f[0], f[1]), 0) + 1
+        print(switches, kernels)
+
+
+def test_the_tokenizer_table_is_what_the_host_tokenizer_reads():
+    """every regular case of tests/tok_cases.py: the rows, positions and scaffold runs it expects by construction are the host
+    tokenizer's (genoio.encode) of its text, and the text is regular by the rule the device tokenizer states"""
+    for c in tok_table():
+        w = genoio.encode(c.text, c.lay)
+        assert w.n_sites == c.n_lines and np.array_equal(w.gt, c.rows), c.name
+        assert np.array_equal(w.pos, c.pos) and list(w.run_starts) == list(c.run_starts) and list(w.run_names) == c.run_names, c.name
+        assert TC.is_regular(c.text, c.n_cols), c.name
+
+
+def test_the_tokenizer_table_holds_what_it_promises():
+    """conditions on the table, not on the code: from five cells on a case's expected rows hold all four codes and zeros (the
+    handful of smaller cases -- one line of one or two columns -- cannot) and at least 80 % of them are called; every byte 33 .. 255 is
+    an allele character somewhere in the non-diplo cases and a diplo character somewhere in the diplo cases; no text reaches 1 MB"""
+    seen, seen_diplo, small = np.zeros(256, dtype=bool), np.zeros(256, dtype=bool), []
+    for c in tok_table():
+        (seen_diplo if c.spec.fmt == "diplo" else seen)[c.allele_bytes.ravel()] = True
+        assert len(c.text) < 1000000, c.name
+        if c.rows.size < 5:
+            small.append(c)
+            continue
+        assert set(np.unique(c.rows).tolist()) == {0, 1, 2, 4, 8}, c.name
+        assert np.count_nonzero(c.rows) >= 0.8 * c.rows.size, c.name
+    assert seen[33:].all() and seen_diplo[33:].all()
+    assert len(small) <= 20 and all(c.n_lines == 1 and c.n_cols <= 2 for c in small), [c.name for c in small]
+
+
+def test_the_tokenizer_tables_defective_twins_are_defective():
+    """every twin of tests/tok_cases.py breaks the device tokenizer's regularity rule (so the device must refuse it) while its base
+    keeps it.  What the host tokenizer makes of a twin: a doubled tab and an inserted `#` line it reads as the base (it skips runs
+    of blanks and comments: the device is the stricter of the two); a line turned into a comment is a row less; a 19-digit position
+    and a missing separator it rejects; a short cell or a blank inside a cell it rejects or reads differently, unless the column is
+    one the layout does not want"""
+    n = 0
+    for sp in TC.refusal_bases():
+        c = TC.build(sp)
+        base = genoio.encode(c.text, c.lay)
+        assert TC.is_regular(c.text, c.n_cols) and np.array_equal(base.gt, c.rows)
+        kinds = set()
+        for label, kind, col, text in TC.twins(c):
+            assert not TC.is_regular(text, c.n_cols), (c.name, label)
+            try:
+                w = genoio.encode(text, c.lay)
+                same = w.n_sites == base.n_sites and np.array_equal(w.gt, base.gt) and np.array_equal(w.pos, base.pos)
+                outcome = "same" if same else "differs"
+            except _lib.PopgenError:
+                outcome = "rejected"
+            if kind in ("tabtab", "comment-line"):
+                assert outcome == "same", (c.name, label, outcome)
+            elif kind == "comment":
+                assert outcome == "differs" and w.n_sites == base.n_sites - 1, (c.name, label, outcome)
+            elif kind in ("pos19", "nosep"):
+                assert outcome == "rejected", (c.name, label, outcome)
+            else:
+                assert outcome != "same" or not c.wanted_col[col], (c.name, label, outcome)
+            kinds.add(kind)
+            n += 1
+        assert kinds == set(TC.DEFECTS) | {"pos19", "comment", "comment-line"}, (c.name, kinds)
+    assert n > 300
