@@ -3,6 +3,7 @@
 #include "../../include/popgen_hip.h"
 #include "pg_internal.h"
 #include "pg_inflate.h"
+#include "pg_line_slot.h"
 #include "pg_vcf_core.h"
 #include "pg_filter_core.h"
 
@@ -86,7 +87,16 @@ struct HostPin {
     }
 };
 
+// what the slots of the per-line device routes share (pg_line_slot.h; the pg_line_* helpers of pg_line_slot.hip work on it)
+struct PgLineDev {
+    DevBuf<int64_t> status;              // PGL_STATUS_WORDS words, raised by the route's kernels
+    HostPin<int64_t> h_status;           //   preset before, copied back behind them
+    hipEvent_t done = nullptr;           // the block's last copy back
+    PgLineSlot L;
+};
+
 struct pg_ctx {
+    using LineSlot = PgLineDev;
     int device = 0;
     hipStream_t stream = nullptr;
     // samples
@@ -172,17 +182,14 @@ struct pg_ctx {
         DevBuf<uint8_t> contigs, ploidy, fsel, prevkey;      // prevkey: the PgvKey of the last data line seen (--excludeDuplicates)
         DevBuf<int32_t> sel_col;
         DevBuf<uint32_t> cell_off;
-        struct Slot {
+        struct Slot : LineSlot {
             DevBuf<uint8_t> lines, out;
             DevBuf<uint32_t> rlen;
-            DevBuf<int64_t> roff, status;        // status: [0] bits (1 a line needs the host, 2 the rows exceed `out`), [1] first such line, [2] bytes of the rows, [3] rows, [4] bytes of the rows as BGZF members
+            DevBuf<int64_t> roff;
             Deflate df;                          // the rows deflated where they lie (pg_vcf_dev_set_output)
-            HostPin<int64_t> h_status;
             HostPin<uint8_t> h_prev;             // the key the block started from
-            hipEvent_t done = nullptr, rows_ready = nullptr;
-            int state = 0;                       // 0 idle, 1 text on its way / there, 2 kernels queued, 3 empty block
-            int64_t text_len = 0, out_cap = 0;
-            bool no_final_newline = false;
+            hipEvent_t rows_ready = nullptr;
+            int64_t out_cap = 0;
         } s[2];
         bool bgzf_rows = false;                  // pg_vcf_dev_set_output: the rows leave the device as BGZF members
         double kernel_ms = 0;                    // pg_vcf_dev_stats
@@ -196,17 +203,12 @@ struct pg_ctx {
         DevBuf<int32_t> sel_col, sel_ploidy;
         DevBuf<uint32_t> sel_popmask, coff;                 // coff: the contig names' offsets (n_contigs + 1)
         DevBuf<uint8_t> contigs, cflags;
-        struct Slot {
+        struct Slot : LineSlot {
             DevBuf<uint8_t> flags, out;
             DevBuf<uint32_t> rlen;
-            DevBuf<int64_t> roff, pos, status;             // status: [0] bits (1 a line needs the host, 2 the rows exceed `out`), [1] first such line, [2] bytes of the rows, [3] rows, [4] bytes of the rows as BGZF members
+            DevBuf<int64_t> roff, pos;
             Deflate df;                                    // the rows deflated where they lie (pg_filter_dev_set_output)
-            HostPin<int64_t> h_status;
-            int64_t n_lines = 0;
-            hipEvent_t done = nullptr;
-            int state = 0;                                 // 0 idle, 1 text there, 2 kernels queued, 3 empty block
-            int64_t text_len = 0, out_cap = 0, first_line = 0;
-            bool no_final_newline = false;
+            int64_t out_cap = 0, first_line = 0;
         } s[2];
         bool bgzf_rows = false;
         int64_t blocks = 0, host_blocks = 0;
@@ -218,15 +220,13 @@ struct pg_ctx {
         pg_seq_cfg cfg;
         int tile_seqs = 0;                                 // output sequences per tile of k_seq_tile
         DevBuf<int32_t> sel_col, sel_off, sel_len;
-        struct Slot {
+        struct Slot : LineSlot {
             DevBuf<uint32_t> keep;                         // per line: 1 a site, 0 a '#' line
             DevBuf<uint8_t> runf, rrun, out;               // runf / rrun: the scaffold differs from the site before, per line / per site
-            DevBuf<int64_t> row, pos, rpos, rstart, line_of, status;   // status: [0] bits (1 a line needs the host), [1] first such line, [3] sites
-            HostPin<int64_t> h_status;
-            int64_t n_lines = 0, text_len = 0, pitch = 0;
-            hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
-            int state = 0;                                 // 0 idle, 1 text there, 2 kernels queued, 3 empty block
-            bool no_final_newline = false, timed = false;
+            DevBuf<int64_t> row, pos, rpos, rstart, line_of;
+            int64_t pitch = 0;
+            hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
+            bool timed = false;
         } s[2];
         bool timing = false;
         double lines_ms = 0, tile_ms = 0;

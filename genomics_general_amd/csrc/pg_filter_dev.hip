@@ -18,12 +18,6 @@
 #include <algorithm>
 #include <cstring>
 
-int pg_tok_text_submit(pg_ctx *c, int slot, const char *text, int fd, int64_t file_offset, int64_t len);
-int pg_tok_lines(pg_ctx *c, int slot, int64_t *n_lines_out);
-int pg_tok_bgzf_submit(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
-                       const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
-                       int64_t text_len, int64_t line_len_hint);
-int pg_tok_crc_result(pg_ctx *c, int slot);
 int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
                      const long long *status_d, long long *comp_total_d);
 void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
@@ -134,7 +128,7 @@ __global__ __launch_bounds__(64) void k_filt_lines(FiltArgs A, PgfConfig cfg) {
     const int lane = (int)threadIdx.x;
     const int64_t i = blockIdx.x;
     if (i >= A.n_lines) return;
-    if (RENDER && (A.rlen[i] == 0 || A.status[0] != 0)) return;   // (a raised status: the block is the host's, its rows are not written)
+    if (RENDER && (A.rlen[i] == 0 || A.status[PGL_ST_BITS] != 0)) return;   // (a raised status: the block is the host's, its rows are not written)
     const int64_t ls = i ? A.nl[i - 1] + 1 : 0, le = A.nl[i];
     const uint8_t *line = A.text + ls;
     if (le - ls > 0x7fffffffll) {
@@ -263,11 +257,7 @@ __global__ __launch_bounds__(64) void k_filt_thin(FiltArgs A, PgfConfig cfg) {
     }
 }
 
-int check_slot(pg_ctx *c, int slot, const char *who) {
-    if (!c || slot < 0 || slot > 1) return pg_fail(PG_ERR_ARG, "%s: bad context or slot", who);
-    if (!c->filt.configured) return pg_fail(PG_ERR_STATE, "%s: pg_filter_dev_config must be called first", who);
-    return PG_OK;
-}
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->filt.configured, who, "pg_filter_dev_config"); }
 
 }  // namespace
 
@@ -321,12 +311,8 @@ extern "C" int pg_filter_dev_submit(pg_ctx *c, int slot, const char *text, int64
     pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
     if (c->filt.cfg.thin_dist && first_line % c->filt.cfg.pod_size)
         return pg_fail(PG_ERR_ARG, "pg_filter_dev_submit: with --thinDist a block starts at a pod (line %lld)", (long long)first_line);
-    F.text_len = len;
     F.first_line = first_line;
-    F.no_final_newline = len > 0 && text[len - 1] != '\n';
-    if ((rc = pg_tok_text_submit(c, slot, text, -1, 0, len)) != PG_OK) return rc;
-    F.state = len ? 1 : 3;
-    return PG_OK;
+    return pg_line_submit_text(c, slot, F, text, -1, 0, len, len > 0 && text[len - 1] == '\n');
 }
 
 // The same for a block that is still bgzipped: the members cross PCIe deflated, k_inflate writes their text behind `head` in the slot
@@ -340,13 +326,8 @@ extern "C" int pg_filter_dev_submit_bgzf(pg_ctx *c, int slot, const uint8_t *com
     if (c->filt.cfg.thin_dist) return pg_fail(PG_ERR_ARG, "pg_filter_dev_submit_bgzf: not with --thinDist (pods are cut in text)");
     if (first_line < 0 || text_len < 0) return pg_fail(PG_ERR_ARG, "pg_filter_dev_submit_bgzf: bad argument");
     pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
-    F.text_len = text_len;
     F.first_line = first_line;
-    F.no_final_newline = false;                                   // (checked in pg_filter_dev_parse)
-    if ((rc = pg_tok_bgzf_submit(c, slot, comp, comp_len, in_off, in_len, out_len, crc, n_members, head, head_len, text_len, 1024)) != PG_OK)
-        return rc;
-    F.state = text_len ? 1 : 3;
-    return PG_OK;
+    return pg_line_submit_bgzf(c, slot, F, comp, comp_len, in_off, in_len, out_len, crc, n_members, head, head_len, text_len, 1024, false, false);
 }
 
 // bgzf_members != 0: the rows of every block filtered from now on are also deflated on the device (k_deflate: BGZF members of 65 280
@@ -366,7 +347,7 @@ FiltArgs filt_args(pg_ctx *c, int slot) {
     FiltArgs A;
     A.text = T.tp;
     A.nl = T.nl.p;
-    A.n_lines = F.n_lines;
+    A.n_lines = F.L.n_lines;
     A.sel_col = D.sel_col.p;
     A.sel_ploidy = D.sel_ploidy.p;
     A.sel_popmask = D.sel_popmask.p;
@@ -384,20 +365,18 @@ FiltArgs filt_args(pg_ctx *c, int slot) {
 
 size_t filt_lds(const PgfConfig &cfg) { return (size_t)cfg.n_cols * 4 + (size_t)cfg.n_pops * sizeof(PgfCounts); }
 
-// the rows' text (k_filt_lines<1>) and, for -o x.gz, their members (k_deflate), then the status back to the host
+// the rows' text (k_filt_lines<1>) and, for -o x.gz, their members (k_deflate), then the status back to the host (the block: queued)
 int queue_render(pg_ctx *c, int slot, hipStream_t st) {
     pg_ctx::FiltDev &D = c->filt;
     pg_ctx::FiltDev::Slot &F = D.s[slot];
     const FiltArgs A = filt_args(c, slot);
-    hipLaunchKernelGGL((k_filt_lines<1>), dim3((unsigned)F.n_lines), dim3(64), filt_lds(D.cfg), st, A, D.cfg);
+    hipLaunchKernelGGL((k_filt_lines<1>), dim3((unsigned)F.L.n_lines), dim3(64), filt_lds(D.cfg), st, A, D.cfg);
     HIPCHK(hipGetLastError());
     if (D.bgzf_rows) {
-        int rc = pg_deflate_queue(c, st, F.df, F.out.p, A.status + 2, F.out_cap, A.status, A.status + 4);
+        int rc = pg_deflate_queue(c, st, F.df, F.out.p, A.status + PGL_ST_BYTES, F.out_cap, A.status, A.status + PGL_ST_BGZF_BYTES);
         if (rc != PG_OK) return rc;
     }
-    HIPCHK(hipMemcpyAsync(F.h_status.p, F.status.p, 40, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(F.done, st));
-    return PG_OK;
+    return pg_line_parse_end(c, F, st);
 }
 
 }  // namespace
@@ -408,32 +387,12 @@ extern "C" int pg_filter_dev_parse(pg_ctx *c, int slot) {
     if (rc != PG_OK) return rc;
     pg_ctx::FiltDev &D = c->filt;
     pg_ctx::FiltDev::Slot &F = D.s[slot];
-    if (F.state == 3) return PG_OK;
-    if (F.state != 1) return pg_fail(PG_ERR_STATE, "pg_filter_dev_parse: nothing submitted to slot %d", slot);
-    HIPCHK(hipSetDevice(c->device));
+    // a block without a final line feed (the file's partial last line) is the host's; a '\r' in a line sends it there too (k_filt_lines)
+    int64_t n_lines = 0;
+    bool nothing = true;
+    if ((rc = pg_line_parse_begin(c, slot, F, &n_lines, &nothing, "pg_filter_dev_parse")) != PG_OK || nothing) return rc;
     hipStream_t st = c->stream_up;
     pg_ctx::TokSlot &T = c->tok[slot];
-    int64_t n_lines = 0;
-    if ((rc = pg_tok_lines(c, slot, &n_lines)) != PG_OK) { F.state = 0; return rc; }
-    F.n_lines = n_lines;
-    if ((rc = F.status.ensure(5)) != PG_OK || (rc = F.h_status.ensure(5)) != PG_OK) return rc;
-    if (!F.done) HIPCHK(hipEventCreateWithFlags(&F.done, hipEventDisableTiming));
-    if (T.deflated && n_lines > 0) {                              // does the inflated text end in a line feed (the file's last block may not)?
-        int64_t last = -1;
-        HIPCHK(hipMemcpyAsync(&last, T.nl.p + n_lines - 1, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        F.no_final_newline = last != F.text_len - 1;
-    }
-    // a block without a final line feed (the file's partial last line) is the host's; a '\r' in a line sends it there too (k_filt_lines)
-    const bool host_now = F.no_final_newline || n_lines == 0;
-    F.h_status.p[0] = host_now ? PG_ST_HOST : 0;
-    F.h_status.p[1] = host_now ? 0 : 0x7fffffffffffffffll;
-    F.h_status.p[2] = F.h_status.p[3] = F.h_status.p[4] = 0;
-    if (host_now) {
-        F.state = 2;
-        HIPCHK(hipEventRecord(F.done, st));
-        return PG_OK;
-    }
     if ((rc = F.flags.ensure_roomy((size_t)n_lines)) != PG_OK || (rc = F.rlen.ensure_roomy((size_t)n_lines)) != PG_OK ||
         (rc = F.roff.ensure_roomy((size_t)n_lines)) != PG_OK || (rc = F.pos.ensure_roomy((size_t)n_lines)) != PG_OK)
         return rc;
@@ -441,7 +400,7 @@ extern "C" int pg_filter_dev_parse(pg_ctx *c, int slot) {
     F.out_cap = std::max<int64_t>(F.out_cap, T.len + n_lines * 16 + 4096);
     if ((rc = F.out.ensure_roomy((size_t)F.out_cap + 64)) != PG_OK) return rc;
     F.out_cap = (int64_t)F.out.cap - 64;                          // (k_deflate reads 32 bytes past the rows)
-    HIPCHK(hipMemcpyAsync(F.status.p, F.h_status.p, 40, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(F.status.p, F.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
     const FiltArgs A = filt_args(c, slot);
     hipLaunchKernelGGL((k_filt_lines<0>), dim3((unsigned)n_lines), dim3(64), filt_lds(D.cfg), st, A, D.cfg);
     if (D.cfg.thin_dist) {
@@ -450,7 +409,6 @@ extern "C" int pg_filter_dev_parse(pg_ctx *c, int slot) {
     }
     pg_rows_scan_queue(st, F.rlen.p, n_lines, F.roff.p, A.status, F.out_cap);
     if ((rc = queue_render(c, slot, st)) != PG_OK) return rc;
-    F.state = 2;
     ++D.blocks;
     return PG_OK;
 }
@@ -468,39 +426,26 @@ extern "C" int pg_filter_dev_collect(pg_ctx *c, int slot, int64_t *rows_len_out,
     *host_line_out = -1;
     if (bgzf_len_out) *bgzf_len_out = 0;
     if (n_lines_out) *n_lines_out = 0;
-    if (F.state == 3) { F.state = 0; return PG_OK; }
-    if (F.state != 2) return pg_fail(PG_ERR_STATE, "pg_filter_dev_collect: nothing parsed in slot %d", slot);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(F.done));
-    F.state = 0;
-    if (n_lines_out) *n_lines_out = F.n_lines;
-    if ((rc = pg_tok_crc_result(c, slot)) != PG_OK) return rc;
-    if (F.h_status.p[0] == PG_ST_OVERFLOW) {                     // only the rows' room: grow it, render again
+    const bool empty = F.L.state == PGL_EMPTY;
+    if ((rc = pg_line_collect_wait(c, slot, F, "pg_filter_dev_collect")) != PG_OK || empty) return rc;
+    if (n_lines_out) *n_lines_out = F.L.n_lines;
+    if (F.h_status.p[PGL_ST_BITS] == PG_ST_OVERFLOW) {           // only the rows' room: grow it, render again
         hipStream_t st = c->stream_up;
-        if ((rc = F.out.ensure_roomy((size_t)F.h_status.p[2] + 4096 + 64)) != PG_OK) return rc;
+        if ((rc = F.out.ensure_roomy((size_t)F.h_status.p[PGL_ST_BYTES] + 4096 + 64)) != PG_OK) return rc;
         F.out_cap = (int64_t)F.out.cap - 64;
-        F.h_status.p[0] = 0;
-        F.h_status.p[4] = 0;
-        HIPCHK(hipMemcpyAsync(F.status.p, F.h_status.p, 40, hipMemcpyHostToDevice, st));
+        F.h_status.p[PGL_ST_BITS] = 0;
+        F.h_status.p[PGL_ST_BGZF_BYTES] = 0;
+        HIPCHK(hipMemcpyAsync(F.status.p, F.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
         if ((rc = queue_render(c, slot, st)) != PG_OK) return rc;
         HIPCHK(hipEventSynchronize(F.done));
+        F.L.state = PGL_IDLE;
     }
-    if (F.h_status.p[0]) {
-        *host_line_out = (F.h_status.p[0] & PG_ST_HOST) ? F.h_status.p[1] : 0;
-        ++c->filt.host_blocks;
-        return PG_OK;
-    }
-    *rows_len_out = F.h_status.p[2];
-    *n_rows_out = F.h_status.p[3];
-    if (bgzf_len_out && c->filt.bgzf_rows) *bgzf_len_out = F.h_status.p[4];
-    return PG_OK;
-}
-
-static int copy_back(pg_ctx *c, uint8_t *dst, const void *src, int64_t len) {
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
-    HIPCHK(hipMemcpyAsync(dst, src, (size_t)len, hipMemcpyDeviceToHost, c->tok_small));   // (beside the next block's kernels on stream_up)
-    HIPCHK(hipStreamSynchronize(c->tok_small));
+    const PgLineResult R = pgl_decode(F.h_status.p, c->filt.bgzf_rows);
+    *host_line_out = R.host_line;
+    *rows_len_out = R.bytes;
+    *n_rows_out = R.rows;
+    if (bgzf_len_out) *bgzf_len_out = R.bgzf_bytes;
+    if (R.host_block) ++c->filt.host_blocks;
     return PG_OK;
 }
 
@@ -509,7 +454,7 @@ extern "C" int pg_filter_dev_rows(pg_ctx *c, int slot, uint8_t *dst, int64_t len
     if (rc != PG_OK) return rc;
     pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
     if (len < 0 || (len && !dst) || (size_t)len > F.out.cap) return pg_fail(PG_ERR_ARG, "pg_filter_dev_rows: bad length");
-    return len ? copy_back(c, dst, F.out.p, len) : PG_OK;
+    return len ? pg_copy_back(c, dst, F.out.p, len) : PG_OK;
 }
 
 extern "C" int pg_filter_dev_rows_bgzf(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
@@ -517,7 +462,7 @@ extern "C" int pg_filter_dev_rows_bgzf(pg_ctx *c, int slot, uint8_t *dst, int64_
     if (rc != PG_OK) return rc;
     pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
     if (len < 0 || (len && !dst) || (size_t)len > F.df.comp.cap) return pg_fail(PG_ERR_ARG, "pg_filter_dev_rows_bgzf: bad length");
-    return len ? copy_back(c, dst, F.df.comp.p, len) : PG_OK;
+    return len ? pg_copy_back(c, dst, F.df.comp.p, len) : PG_OK;
 }
 
 // the text of the collected block -> dst (a block that goes to the host route and whose text the host never had: BGZF)
@@ -526,7 +471,7 @@ extern "C" int pg_filter_dev_text(pg_ctx *c, int slot, uint8_t *dst, int64_t len
     if (rc != PG_OK) return rc;
     pg_ctx::TokSlot &T = c->tok[slot];
     if (len < 0 || (len && !dst) || len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_filter_dev_text: bad length");
-    return len ? copy_back(c, dst, T.tp, len) : PG_OK;
+    return len ? pg_copy_back(c, dst, T.tp, len) : PG_OK;
 }
 
 extern "C" int pg_filter_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out) {

@@ -116,6 +116,36 @@ void pg_launch_popstats(hipStream_t st, const double *sums, const int64_t *cnts,
                         int n_pops, double min_data, int do_pairs, double *out, const int64_t *win_lo = nullptr,
                         const int64_t *win_hi = nullptr, long long skip_upto = -1);
 
+// ---- a block of whole lines through one of the tokenizer's two text slots ---------------------------------
+struct pg_ctx;
+struct PgLineDev;               // pg_ctx::LineSlot (pg_ctx.h)
+// pg_tokenize.hip: the text (or its deflated members) to the device, line feeds counted behind it; the wait for the count, the line
+// feeds' positions queued; the members' checksums of a block whose kernels have finished
+int pg_tok_text_submit(pg_ctx *c, int slot, const char *text, int fd, int64_t file_offset, int64_t len);
+int pg_tok_bgzf_submit(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                       const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                       int64_t text_len, int64_t line_len_hint);
+int pg_tok_lines(pg_ctx *c, int slot, int64_t *n_lines_out);
+int pg_tok_crc_result(pg_ctx *c, int slot);
+// pg_line_slot.hip: the protocol of pg_line_slot.h carried out for the per-line routes (`who`: the entry point, for the error texts).
+// c->tok_small, made on first use
+int pg_small_stream(pg_ctx *c);
+// len bytes device -> host on the small stream (beside the next block's kernels on the copy stream), waited for
+int pg_copy_back(pg_ctx *c, void *dst, const void *src, int64_t len);
+int pg_line_check_slot(pg_ctx *c, int slot, bool configured, const char *who, const char *config_name);
+int pg_line_submit_text(pg_ctx *c, int slot, PgLineDev &S, const char *text, int fd, int64_t file_offset, int64_t len, bool last_is_newline);
+// last_known = false: whether the text ends in a line feed is read on the device in parse (a stream synchronisation more)
+int pg_line_submit_bgzf(pg_ctx *c, int slot, PgLineDev &S, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off,
+                        const uint32_t *in_len, const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head,
+                        int64_t head_len, int64_t text_len, int64_t line_len_hint, bool last_known, bool last_is_newline);
+// everything of parse in front of the route's kernels.  *nothing_out: there is nothing for the route to queue (an empty block --
+// S.L.state stays PGL_EMPTY --, or one that is the host's as it stands -- queued, S.done recorded)
+int pg_line_parse_begin(pg_ctx *c, int slot, PgLineDev &S, int64_t *n_lines_out, bool *nothing_out, const char *who);
+// behind the route's kernels: the status words back on `st`, S.done recorded there, queued
+int pg_line_parse_end(pg_ctx *c, PgLineDev &S, hipStream_t st);
+// the head of collect: the state checked, S.done waited for, idle, the members' checksums.  An empty block: idle, nothing else
+int pg_line_collect_wait(pg_ctx *c, int slot, PgLineDev &S, const char *who);
+
 // ---- shared device routines ---------------------------------------------------------------------------
 // float64 sum in the order NumPy's add.reduce visits a contiguous array, by one lane (k_hapstats: the reference's
 // `(clusterFreq**2).sum()`, genomics.py:1088-1091; k_paint: np.nanmean of a population's distances): fewer than 8 elements left to

@@ -21,12 +21,6 @@
 #include <algorithm>
 #include <cstring>
 
-int pg_tok_text_submit(pg_ctx *c, int slot, const char *text, int fd, int64_t file_offset, int64_t len);
-int pg_tok_lines(pg_ctx *c, int slot, int64_t *n_lines_out);
-int pg_tok_bgzf_submit(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
-                       const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
-                       int64_t text_len, int64_t line_len_hint);
-int pg_tok_crc_result(pg_ctx *c, int slot);
 void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
 
 namespace {
@@ -182,11 +176,7 @@ __global__ __launch_bounds__(PGS_TILE_THREADS) void k_seq_tile(SeqArgs A, pg_seq
     }
 }
 
-int check_slot(pg_ctx *c, int slot, const char *who) {
-    if (!c || slot < 0 || slot > 1) return pg_fail(PG_ERR_ARG, "%s: bad context or slot", who);
-    if (!c->seq.configured) return pg_fail(PG_ERR_STATE, "%s: pg_seq_dev_config must be called first", who);
-    return PG_OK;
-}
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->seq.configured, who, "pg_seq_dev_config"); }
 
 SeqArgs seq_args(pg_ctx *c, int slot) {
     pg_ctx::SeqDev &D = c->seq;
@@ -195,7 +185,7 @@ SeqArgs seq_args(pg_ctx *c, int slot) {
     SeqArgs A;
     A.text = T.tp;
     A.nl = T.nl.p;
-    A.n_lines = Q.n_lines;
+    A.n_lines = Q.L.n_lines;
     A.pitch = Q.pitch;
     A.sel_col = D.sel_col.p;
     A.sel_off = D.sel_off.p;
@@ -212,14 +202,6 @@ SeqArgs seq_args(pg_ctx *c, int slot) {
     A.status = reinterpret_cast<long long *>(Q.status.p);
     A.tile_seqs = D.tile_seqs;
     return A;
-}
-
-int copy_back(pg_ctx *c, void *dst, const void *src, int64_t len) {
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
-    HIPCHK(hipMemcpyAsync(dst, src, (size_t)len, hipMemcpyDeviceToHost, c->tok_small));   // (beside the next block's kernels on stream_up)
-    HIPCHK(hipStreamSynchronize(c->tok_small));
-    return PG_OK;
 }
 
 }  // namespace
@@ -257,12 +239,7 @@ extern "C" int pg_seq_dev_submit(pg_ctx *c, int slot, const char *text, int64_t 
     int rc = check_slot(c, slot, "pg_seq_dev_submit");
     if (rc != PG_OK) return rc;
     if ((!text && len) || len < 0) return pg_fail(PG_ERR_ARG, "pg_seq_dev_submit: no text");
-    pg_ctx::SeqDev::Slot &Q = c->seq.s[slot];
-    Q.text_len = len;
-    Q.no_final_newline = len > 0 && text[len - 1] != '\n';
-    if ((rc = pg_tok_text_submit(c, slot, text, -1, 0, len)) != PG_OK) return rc;
-    Q.state = len ? 1 : 3;
-    return PG_OK;
+    return pg_line_submit_text(c, slot, c->seq.s[slot], text, -1, 0, len, len > 0 && text[len - 1] == '\n');
 }
 
 // The same for a block that is still bgzipped: the members cross PCIe deflated, k_inflate writes their text behind `head` in the slot
@@ -274,13 +251,8 @@ extern "C" int pg_seq_dev_submit_bgzf(pg_ctx *c, int slot, const uint8_t *comp, 
     int rc = check_slot(c, slot, "pg_seq_dev_submit_bgzf");
     if (rc != PG_OK) return rc;
     if (text_len < 0) return pg_fail(PG_ERR_ARG, "pg_seq_dev_submit_bgzf: bad argument");
-    pg_ctx::SeqDev::Slot &Q = c->seq.s[slot];
-    Q.text_len = text_len;
-    Q.no_final_newline = false;                                   // (checked in pg_seq_dev_parse)
-    if ((rc = pg_tok_bgzf_submit(c, slot, comp, comp_len, in_off, in_len, out_len, crc, n_members, head, head_len, text_len, 1024)) != PG_OK)
-        return rc;
-    Q.state = text_len ? 1 : 3;
-    return PG_OK;
+    return pg_line_submit_bgzf(c, slot, c->seq.s[slot], comp, comp_len, in_off, in_len, out_len, crc, n_members, head, head_len, text_len, 1024,
+                               false, false);
 }
 
 // Queues the kernels of the block in `slot` (waits for the number of its lines only)
@@ -289,34 +261,14 @@ extern "C" int pg_seq_dev_parse(pg_ctx *c, int slot) {
     if (rc != PG_OK) return rc;
     pg_ctx::SeqDev &D = c->seq;
     pg_ctx::SeqDev::Slot &Q = D.s[slot];
-    if (Q.state == 3) return PG_OK;
-    if (Q.state != 1) return pg_fail(PG_ERR_STATE, "pg_seq_dev_parse: nothing submitted to slot %d", slot);
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->stream_up;
-    pg_ctx::TokSlot &T = c->tok[slot];
-    int64_t n_lines = 0;
-    if ((rc = pg_tok_lines(c, slot, &n_lines)) != PG_OK) { Q.state = 0; return rc; }
-    Q.n_lines = n_lines;
-    Q.pitch = pgs_pitch(n_lines);
-    if ((rc = Q.status.ensure(5)) != PG_OK || (rc = Q.h_status.ensure(5)) != PG_OK) return rc;
-    if (!Q.done) HIPCHK(hipEventCreateWithFlags(&Q.done, hipEventDisableTiming));
-    if (T.deflated && n_lines > 0) {                              // does the inflated text end in a line feed (the file's last block may not)?
-        int64_t last = -1;
-        HIPCHK(hipMemcpyAsync(&last, T.nl.p + n_lines - 1, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        Q.no_final_newline = last != Q.text_len - 1;
-    }
     // a block without a final line feed (the file's partial last line) is the host's
-    const bool host_now = Q.no_final_newline || n_lines == 0;
-    Q.h_status.p[0] = host_now ? PG_ST_HOST : 0;
-    Q.h_status.p[1] = host_now ? 0 : 0x7fffffffffffffffll;
-    Q.h_status.p[2] = Q.h_status.p[3] = Q.h_status.p[4] = 0;
+    int64_t n_lines = 0;
+    bool nothing = true;
+    if ((rc = pg_line_parse_begin(c, slot, Q, &n_lines, &nothing, "pg_seq_dev_parse")) != PG_OK || Q.L.state == PGL_EMPTY) return rc;
+    Q.pitch = pgs_pitch(n_lines);
     Q.timed = false;
-    if (host_now) {
-        Q.state = 2;
-        HIPCHK(hipEventRecord(Q.done, st));
-        return PG_OK;
-    }
+    if (nothing) return PG_OK;
+    hipStream_t st = c->stream_up;
     const size_t nl = (size_t)n_lines;
     if ((rc = Q.keep.ensure_roomy(nl)) != PG_OK || (rc = Q.runf.ensure_roomy(nl)) != PG_OK || (rc = Q.rrun.ensure_roomy(nl)) != PG_OK ||
         (rc = Q.row.ensure_roomy(nl)) != PG_OK || (rc = Q.pos.ensure_roomy(nl)) != PG_OK || (rc = Q.rpos.ensure_roomy(nl)) != PG_OK ||
@@ -327,7 +279,7 @@ extern "C" int pg_seq_dev_parse(pg_ctx *c, int slot) {
         for (hipEvent_t *e : {&Q.t0, &Q.t1, &Q.t2, &Q.t3})
             if (!*e) HIPCHK(hipEventCreate(e));
     }
-    HIPCHK(hipMemcpyAsync(Q.status.p, Q.h_status.p, 40, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(Q.status.p, Q.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
     // the matrix's pad bytes (behind the last site of a sequence, up to the pitch) are zero whatever the slot held before
     HIPCHK(hipMemsetAsync(Q.out.p, 0, (size_t)D.cfg.n_seq * (size_t)Q.pitch, st));
     const SeqArgs A = seq_args(c, slot);
@@ -348,9 +300,7 @@ extern "C" int pg_seq_dev_parse(pg_ctx *c, int slot) {
         HIPCHK(hipEventRecord(Q.t3, st));
         Q.timed = true;
     }
-    HIPCHK(hipMemcpyAsync(Q.h_status.p, Q.status.p, 40, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(Q.done, st));
-    Q.state = 2;
+    if ((rc = pg_line_parse_end(c, Q, st)) != PG_OK) return rc;
     ++D.blocks;
     return PG_OK;
 }
@@ -364,14 +314,10 @@ extern "C" int pg_seq_dev_collect(pg_ctx *c, int slot, int64_t *n_sites_out, int
     *host_line_out = -1;
     if (n_lines_out) *n_lines_out = 0;
     if (pitch_out) *pitch_out = 0;
-    if (Q.state == 3) { Q.state = 0; return PG_OK; }
-    if (Q.state != 2) return pg_fail(PG_ERR_STATE, "pg_seq_dev_collect: nothing parsed in slot %d", slot);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(Q.done));
-    Q.state = 0;
-    if (n_lines_out) *n_lines_out = Q.n_lines;
+    const bool empty = Q.L.state == PGL_EMPTY;
+    if ((rc = pg_line_collect_wait(c, slot, Q, "pg_seq_dev_collect")) != PG_OK || empty) return rc;
+    if (n_lines_out) *n_lines_out = Q.L.n_lines;
     if (pitch_out) *pitch_out = Q.pitch;
-    if ((rc = pg_tok_crc_result(c, slot)) != PG_OK) return rc;
     if (Q.timed) {
         float a = 0, b = 0;
         HIPCHK(hipEventElapsedTime(&a, Q.t0, Q.t1));
@@ -380,12 +326,10 @@ extern "C" int pg_seq_dev_collect(pg_ctx *c, int slot, int64_t *n_sites_out, int
         c->seq.tile_ms += b;
         Q.timed = false;
     }
-    if (Q.h_status.p[0]) {
-        *host_line_out = (Q.h_status.p[0] & PG_ST_HOST) ? Q.h_status.p[1] : 0;
-        ++c->seq.host_blocks;
-        return PG_OK;
-    }
-    *n_sites_out = Q.h_status.p[3];
+    const PgLineResult R = pgl_decode(Q.h_status.p, false);
+    *host_line_out = R.host_line;
+    *n_sites_out = R.rows;
+    if (R.host_block) ++c->seq.host_blocks;
     return PG_OK;
 }
 
@@ -398,7 +342,7 @@ extern "C" int pg_seq_dev_rows(pg_ctx *c, int slot, int q0, int q1, uint8_t *dst
         return pg_fail(PG_ERR_ARG, "pg_seq_dev_rows: bad range or width");
     if (q1 == q0 || width == 0) return PG_OK;
     HIPCHK(hipSetDevice(c->device));
-    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
+    if ((rc = pg_small_stream(c)) != PG_OK) return rc;
     HIPCHK(hipMemcpy2DAsync(dst, (size_t)dst_pitch, Q.out.p + (size_t)q0 * (size_t)Q.pitch, (size_t)Q.pitch, (size_t)width, (size_t)(q1 - q0),
                             hipMemcpyDeviceToHost, c->tok_small));
     HIPCHK(hipStreamSynchronize(c->tok_small));
@@ -409,13 +353,13 @@ extern "C" int pg_seq_dev_meta(pg_ctx *c, int slot, int64_t *pos_dst, uint8_t *r
     int rc = check_slot(c, slot, "pg_seq_dev_meta");
     if (rc != PG_OK) return rc;
     pg_ctx::SeqDev::Slot &Q = c->seq.s[slot];
-    const int64_t n = Q.h_status.p ? Q.h_status.p[3] : 0;
-    if (Q.h_status.p && Q.h_status.p[0]) return pg_fail(PG_ERR_STATE, "pg_seq_dev_meta: the block in slot %d is the host's", slot);
+    const int64_t n = Q.h_status.p ? Q.h_status.p[PGL_ST_ROWS] : 0;
+    if (Q.h_status.p && Q.h_status.p[PGL_ST_BITS]) return pg_fail(PG_ERR_STATE, "pg_seq_dev_meta: the block in slot %d is the host's", slot);
     if (n < 0 || (size_t)n > Q.rpos.cap) return pg_fail(PG_ERR_STATE, "pg_seq_dev_meta: nothing collected in slot %d", slot);
     if (n == 0) return PG_OK;
     if (!pos_dst || !run_dst || !start_dst) return pg_fail(PG_ERR_ARG, "pg_seq_dev_meta: null argument");
-    if ((rc = copy_back(c, pos_dst, Q.rpos.p, n * 8)) != PG_OK || (rc = copy_back(c, run_dst, Q.rrun.p, n)) != PG_OK) return rc;
-    return copy_back(c, start_dst, Q.rstart.p, n * 8);
+    if ((rc = pg_copy_back(c, pos_dst, Q.rpos.p, n * 8)) != PG_OK || (rc = pg_copy_back(c, run_dst, Q.rrun.p, n)) != PG_OK) return rc;
+    return pg_copy_back(c, start_dst, Q.rstart.p, n * 8);
 }
 
 // bytes [off, off + len) of the collected block's text (a run's scaffold name; the whole block when it goes to the host route and the
@@ -425,7 +369,7 @@ extern "C" int pg_seq_dev_text(pg_ctx *c, int slot, int64_t off, int64_t len, ui
     if (rc != PG_OK) return rc;
     pg_ctx::TokSlot &T = c->tok[slot];
     if (off < 0 || len < 0 || (len && !dst) || off + len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_seq_dev_text: bad range");
-    return len ? copy_back(c, dst, T.tp + off, len) : PG_OK;
+    return len ? pg_copy_back(c, dst, T.tp + off, len) : PG_OK;
 }
 
 extern "C" int pg_seq_dev_timing(pg_ctx *c, int on) {

@@ -1009,7 +1009,7 @@ static int tok_parse(pg_ctx *c, int slot, int64_t row_offset, int64_t row_capaci
         // has them, beside the cell kernel -- on the copy stream they stood between this block's cells and the next block's k_inflate
         static const bool pos_aside = !(getenv("PG_TOK_POS_STREAM") && atoi(getenv("PG_TOK_POS_STREAM")) == 0);
         if (pos_aside) {
-            if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
+            if (int e = pg_small_stream(c)) return e;
             if (!T.heads_done) HIPCHK(hipEventCreateWithFlags(&T.heads_done, hipEventDisableTiming));
             if (!T.pos_copied) HIPCHK(hipEventCreateWithFlags(&T.pos_copied, hipEventDisableTiming));
             HIPCHK(hipEventRecord(T.heads_done, st));
@@ -1091,7 +1091,7 @@ static int tok_collect(pg_ctx *c, int slot, int64_t *pos_out, int64_t pos_capaci
         HIPCHK(hipEventSynchronize(T.pos_copied));
         T.pos_pending = false;
     }
-    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
+    if (int e = pg_small_stream(c)) return e;
     hipStream_t st = c->tok_small;
     const int64_t n_lines = T.n_lines;
     if (!pos_out || !run_row_out || !run_off_out || !run_len_out || pos_capacity < n_lines)
@@ -1306,7 +1306,7 @@ extern "C" int pg_tokenize_run_names(pg_ctx *c, int slot, const int64_t *run_off
     if (total == 0) return PG_OK;
     HIPCHK(hipSetDevice(c->device));
     // (the block has been collected: its text is complete; the small stream, so that this does not wait for the next block's inflate)
-    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
+    if (int e = pg_small_stream(c)) return e;
     hipStream_t st = c->tok_small;
     int rc;
     const size_t len_words = ((size_t)n_runs * 4 + 7) / 8;           // the int32 lengths ride behind the offsets

@@ -24,12 +24,6 @@
 
 #include <unistd.h>
 
-int pg_tok_text_submit(pg_ctx *c, int slot, const char *text, int fd, int64_t file_offset, int64_t len);
-int pg_tok_bgzf_submit(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
-                       const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
-                       int64_t text_len, int64_t line_len_hint);
-int pg_tok_lines(pg_ctx *c, int slot, int64_t *n_lines_out);
-int pg_tok_crc_result(pg_ctx *c, int slot);
 int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
                      const long long *status_d, long long *comp_total_d);
 
@@ -267,17 +261,13 @@ __global__ __launch_bounds__(1024) void k_vcf_scan(const uint32_t *__restrict__ 
         run += rlen[k];
     }
     if (threadIdx.x == 1023) {
-        status[2] = sh[1023];
-        status[3] = shn[1023];
-        if (sh[1023] > out_cap) atomicOr(reinterpret_cast<unsigned long long *>(status), (unsigned long long)PG_ST_OVERFLOW);
+        status[PGL_ST_BYTES] = sh[1023];
+        status[PGL_ST_ROWS] = shn[1023];
+        if (sh[1023] > out_cap) atomicOr(reinterpret_cast<unsigned long long *>(status + PGL_ST_BITS), (unsigned long long)PG_ST_OVERFLOW);
     }
 }
 
-int check_slot(pg_ctx *c, int slot, const char *who) {
-    if (!c || slot < 0 || slot > 1) return pg_fail(PG_ERR_ARG, "%s: bad context or slot", who);
-    if (!c->vcf.configured) return pg_fail(PG_ERR_STATE, "%s: pg_vcf_dev_config must be called first", who);
-    return PG_OK;
-}
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->vcf.configured, who, "pg_vcf_dev_config"); }
 
 }  // namespace
 
@@ -375,34 +365,22 @@ extern "C" int pg_vcf_dev_submit(pg_ctx *c, int slot, const char *text, int fd, 
     int rc = check_slot(c, slot, "pg_vcf_dev_submit");
     if (rc != PG_OK) return rc;
     if ((!text && fd < 0 && len) || file_offset < 0 || len < 0) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_submit: no text");
-    pg_ctx::VcfDev::Slot &V = c->vcf.s[slot];
-    V.text_len = len;
-    V.no_final_newline = false;
-    if (len > 0) {
-        char last = 0;
-        if (text) last = text[len - 1];
-        else if (pread(fd, &last, 1, (off_t)(file_offset + len - 1)) != 1) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_submit: cannot read the input");
-        V.no_final_newline = last != '\n';                      // (the end of a file without a final line feed: that block is the host's)
-    }
-    if ((rc = pg_tok_text_submit(c, slot, text, fd, file_offset, len)) != PG_OK) return rc;
-    V.state = len ? 1 : 3;
-    return PG_OK;
+    char last = 0;                                               // (the end of a file without a final line feed: that block is the host's)
+    if (len > 0 && text) last = text[len - 1];
+    else if (len > 0 && pread(fd, &last, 1, (off_t)(file_offset + len - 1)) != 1) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_submit: cannot read the input");
+    return pg_line_submit_text(c, slot, c->vcf.s[slot], text, fd, file_offset, len, last == '\n');
 }
 
 // The same for a block that is still bgzipped (the arguments of pg_tokenize_submit_bgzf): the members cross PCIe deflated, k_inflate
-// writes their text behind `head` and lists its line feeds.  Asynchronous when comp is page-locked.
+// writes their text behind `head` and lists its line feeds.  Asynchronous when comp is page-locked.  The caller says whether the text
+// ends in a line feed (last_is_newline): parse does not read it back from the device
 extern "C" int pg_vcf_dev_submit_bgzf(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
                                       const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
                                       int64_t text_len, int64_t line_len_hint, int last_is_newline) {
     int rc = check_slot(c, slot, "pg_vcf_dev_submit_bgzf");
     if (rc != PG_OK) return rc;
-    pg_ctx::VcfDev::Slot &V = c->vcf.s[slot];
-    V.text_len = text_len;
-    V.no_final_newline = text_len > 0 && !last_is_newline;
-    if ((rc = pg_tok_bgzf_submit(c, slot, comp, comp_len, in_off, in_len, out_len, crc, n_members, head, head_len, text_len,
-                                 line_len_hint > 0 ? line_len_hint : 64)) != PG_OK) return rc;
-    V.state = text_len ? 1 : 3;
-    return PG_OK;
+    return pg_line_submit_bgzf(c, slot, c->vcf.s[slot], comp, comp_len, in_off, in_len, out_len, crc, n_members, head, head_len, text_len,
+                               line_len_hint > 0 ? line_len_hint : 64, true, last_is_newline != 0);
 }
 
 // the rows' places of a block (k_vcf_scan), for the other per-line renderers (pg_filter_dev.hip): status [0] bits, [2] bytes, [3] rows
@@ -416,27 +394,17 @@ extern "C" int pg_vcf_dev_parse(pg_ctx *c, int slot) {
     if (rc != PG_OK) return rc;
     pg_ctx::VcfDev &D = c->vcf;
     pg_ctx::VcfDev::Slot &V = D.s[slot];
-    if (V.state == 3) return PG_OK;
-    if (V.state != 1) return pg_fail(PG_ERR_STATE, "pg_vcf_dev_parse: nothing submitted to slot %d", slot);
-    HIPCHK(hipSetDevice(c->device));
+    int64_t n_lines = 0;
+    bool nothing = true;
+    if ((rc = pg_line_parse_begin(c, slot, V, &n_lines, &nothing, "pg_vcf_dev_parse")) != PG_OK || V.L.state == PGL_EMPTY) return rc;
     hipStream_t st = c->stream_up;
     pg_ctx::TokSlot &T = c->tok[slot];
-    int64_t n_lines = 0;
-    if ((rc = pg_tok_lines(c, slot, &n_lines)) != PG_OK) { V.state = 0; return rc; }
-    if ((rc = V.status.ensure(8)) != PG_OK || (rc = V.h_status.ensure(8)) != PG_OK) return rc;
-    if (!V.done) HIPCHK(hipEventCreateWithFlags(&V.done, hipEventDisableTiming));
-    V.h_status.p[0] = V.no_final_newline || n_lines == 0 ? PG_ST_HOST : 0;     // (no line feed at all: one unfinished line)
-    V.h_status.p[1] = V.no_final_newline || n_lines == 0 ? 0 : 0x7fffffffffffffffll;
-    V.h_status.p[2] = V.h_status.p[3] = V.h_status.p[4] = 0;
     if (D.cfg.flags & PGV_EXCLUDE_DUPLICATES) {                  // (the key this block starts from, for a block that goes to the host after all)
         if ((rc = V.h_prev.ensure(sizeof(PgvKey))) != PG_OK) return rc;
         HIPCHK(hipMemcpyAsync(V.h_prev.p, D.prevkey.p, sizeof(PgvKey), hipMemcpyDeviceToHost, st));
+        if (nothing) HIPCHK(hipEventRecord(V.done, st));         // (recorded once more, behind the key: collect waits for both)
     }
-    if (V.h_status.p[0]) {                                       // nothing to queue: collect reports the block as the host's
-        V.state = 2;
-        HIPCHK(hipEventRecord(V.done, st));
-        return PG_OK;
-    }
+    if (nothing) return PG_OK;
     if ((rc = V.lines.ensure_roomy((size_t)n_lines * sizeof(PgvLine))) != PG_OK || (rc = V.rlen.ensure_roomy((size_t)n_lines)) != PG_OK ||
         (rc = V.roff.ensure_roomy((size_t)n_lines)) != PG_OK)
         return rc;
@@ -444,7 +412,7 @@ extern "C" int pg_vcf_dev_parse(pg_ctx *c, int slot) {
     // length again on top of the plain rows' bound, a total beyond it sends the block to the host
     V.out_cap = T.len + n_lines * (int64_t)(D.cfg.plain_cells + 64) + 4096;
     if ((rc = V.out.ensure_roomy((size_t)V.out_cap)) != PG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(V.status.p, V.h_status.p, 40, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(V.status.p, V.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
     PgvLine *lines = reinterpret_cast<PgvLine *>(V.lines.p);
     long long *status = reinterpret_cast<long long *>(V.status.p);
     const PgvKey *prev = reinterpret_cast<const PgvKey *>(D.prevkey.p);
@@ -473,11 +441,9 @@ extern "C" int pg_vcf_dev_parse(pg_ctx *c, int slot) {
             HIPCHK(hipStreamWaitEvent(c->stream2, V.rows_ready, 0));
             fin = c->stream2;
         }
-        if ((rc = pg_deflate_queue(c, fin, V.df, V.out.p, status + 2, V.out_cap, status, status + 4)) != PG_OK) return rc;
+        if ((rc = pg_deflate_queue(c, fin, V.df, V.out.p, status + PGL_ST_BYTES, V.out_cap, status, status + PGL_ST_BGZF_BYTES)) != PG_OK) return rc;
     }
-    HIPCHK(hipMemcpyAsync(V.h_status.p, V.status.p, 40, hipMemcpyDeviceToHost, fin));
-    HIPCHK(hipEventRecord(V.done, fin));
-    V.state = 2;
+    if ((rc = pg_line_parse_end(c, V, fin)) != PG_OK) return rc;
     ++D.blocks;
     return PG_OK;
 }
@@ -492,20 +458,14 @@ extern "C" int pg_vcf_dev_collect(pg_ctx *c, int slot, int64_t *out_len_out, int
     *out_len_out = *n_rows_out = 0;
     *host_line_out = -1;
     if (bgzf_len_out) *bgzf_len_out = 0;
-    if (V.state == 3) { V.state = 0; return PG_OK; }
-    if (V.state != 2) return pg_fail(PG_ERR_STATE, "pg_vcf_dev_collect: nothing parsed in slot %d", slot);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipEventSynchronize(V.done));
-    V.state = 0;
-    if ((rc = pg_tok_crc_result(c, slot)) != PG_OK) return rc;
-    if (V.h_status.p[0]) {
-        *host_line_out = (V.h_status.p[0] & PG_ST_HOST) ? V.h_status.p[1] : 0;
-        ++c->vcf.host_blocks;
-        return PG_OK;
-    }
-    *out_len_out = V.h_status.p[2];
-    *n_rows_out = V.h_status.p[3];
-    if (bgzf_len_out && c->vcf.bgzf_rows) *bgzf_len_out = V.h_status.p[4];
+    const bool empty = V.L.state == PGL_EMPTY;
+    if ((rc = pg_line_collect_wait(c, slot, V, "pg_vcf_dev_collect")) != PG_OK || empty) return rc;
+    const PgLineResult R = pgl_decode(V.h_status.p, c->vcf.bgzf_rows);
+    *host_line_out = R.host_line;
+    *out_len_out = R.bytes;
+    *n_rows_out = R.rows;
+    if (bgzf_len_out) *bgzf_len_out = R.bgzf_bytes;
+    if (R.host_block) ++c->vcf.host_blocks;
     return PG_OK;
 }
 
@@ -522,12 +482,7 @@ extern "C" int pg_vcf_dev_rows_bgzf(pg_ctx *c, int slot, uint8_t *dst, int64_t l
     if (rc != PG_OK) return rc;
     pg_ctx::VcfDev::Slot &V = c->vcf.s[slot];
     if (len < 0 || (len && !dst) || (size_t)len > V.df.comp.cap) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_rows_bgzf: bad length");
-    if (len == 0) return PG_OK;
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
-    HIPCHK(hipMemcpyAsync(dst, V.df.comp.p, (size_t)len, hipMemcpyDeviceToHost, c->tok_small));
-    HIPCHK(hipStreamSynchronize(c->tok_small));
-    return PG_OK;
+    return len ? pg_copy_back(c, dst, V.df.comp.p, len) : PG_OK;
 }
 
 // the rows of the collected block -> dst (len = what collect reported; page-locked dst: one DMA at the link's rate)
@@ -536,12 +491,7 @@ extern "C" int pg_vcf_dev_rows(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     if (rc != PG_OK) return rc;
     pg_ctx::VcfDev::Slot &V = c->vcf.s[slot];
     if (len < 0 || (len && !dst) || (size_t)len > V.out.cap) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_rows: bad length");
-    if (len == 0) return PG_OK;
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
-    HIPCHK(hipMemcpyAsync(dst, V.out.p, (size_t)len, hipMemcpyDeviceToHost, c->tok_small));     // (beside the next block's inflate on the copy stream)
-    HIPCHK(hipStreamSynchronize(c->tok_small));
-    return PG_OK;
+    return len ? pg_copy_back(c, dst, V.out.p, len) : PG_OK;
 }
 
 // the text of the collected block -> dst (a block that goes to the host parser and whose text the host never had: BGZF)
@@ -550,12 +500,7 @@ extern "C" int pg_vcf_dev_text(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     if (rc != PG_OK) return rc;
     pg_ctx::TokSlot &T = c->tok[slot];
     if (len < 0 || (len && !dst) || len > T.len || !T.tp) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_text: bad length");
-    if (len == 0) return PG_OK;
-    HIPCHK(hipSetDevice(c->device));
-    if (!c->tok_small) HIPCHK(hipStreamCreateWithFlags(&c->tok_small, hipStreamNonBlocking));
-    HIPCHK(hipMemcpyAsync(dst, T.tp, (size_t)len, hipMemcpyDeviceToHost, c->tok_small));
-    HIPCHK(hipStreamSynchronize(c->tok_small));
-    return PG_OK;
+    return len ? pg_copy_back(c, dst, T.tp, len) : PG_OK;
 }
 
 // blocks parsed on the device / handed to the host so far

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "pg_line_slot.h"
+
 // inclusive / exclusive prefix sum over the wave's lanes
 __device__ __forceinline__ int pg_wave_incl_scan(int x, int lane) {
 #pragma unroll
@@ -36,11 +38,8 @@ __device__ __forceinline__ uint32_t pg_rl(uint32_t v, int lane) { return (uint32
 __device__ __forceinline__ int pg_rl_any(int v, int lane) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(lane)); }
 __device__ __forceinline__ uint32_t pg_rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
-// status[0]: bits; status[1]: the first line that needs the host parser
-#define PG_ST_HOST 1ll      // some line of the block goes through the host parser
-#define PG_ST_OVERFLOW 2ll  // the rows did not fit the output buffer: grow it, render again
-
+// the status words of a block (pg_line_slot.h): a line that needs the host parser
 __device__ __forceinline__ void pg_raise_host(long long *status, long long line) {
-    atomicOr(reinterpret_cast<unsigned long long *>(status), (unsigned long long)PG_ST_HOST);
-    atomicMin(status + 1, line);
+    atomicOr(reinterpret_cast<unsigned long long *>(status + PGL_ST_BITS), (unsigned long long)PG_ST_HOST);
+    atomicMin(status + PGL_ST_HOST_LINE, line);
 }

@@ -15,7 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, devroute
 from ._lib import check
 
 
@@ -305,12 +305,10 @@ class Engine:
         """a block of bgzip-compressed text (genoio.BgzfSpan) -> device buffer of `slot`: the members cross PCIe deflated and are
         inflated on the device (pg_tokenize_submit_bgzf); False: not the regular layout"""
         lay = self.layout
-        in_off, in_len, out_len, crc = span.tab
         ok = C.c_int(0)
-        vp = lambda a: C.c_void_p(a.ctypes.data)                            # noqa: E731
-        src = (None, int(span.file[0]), int(span.file[1])) if span.file is not None else (vp(span.comp), -1, 0)
-        check(self._L.pg_tokenize_submit_bgzf(self._h, int(slot), src[0], src[1], src[2], len(span.comp), vp(in_off), vp(in_len), vp(out_len), vp(crc),
-                                              len(in_off), span.head, len(span.head), len(span), span.first_line, len(span.first_line),
+        args, _keep = devroute.span_args(span)
+        src = (None, int(span.file[0]), int(span.file[1])) if span.file is not None else (args[0], -1, 0)
+        check(self._L.pg_tokenize_submit_bgzf(self._h, int(slot), *src, *args[1:], span.first_line, len(span.first_line),
                                               _lib.FMT[lay.genoFormat], len(lay.col_ploidy), lay.max_ploidy,
                                               np.ascontiguousarray(lay.col_slot), lay.col_ploidy, C.byref(ok)))
         return bool(ok.value)
@@ -348,12 +346,9 @@ class Engine:
     def vcf_submit(self, slot, block, file=None):
         """a block of whole lines (bytes-like; file = (descriptor, offset) when it is a view of a memory-mapped file: the staging
         threads then read it themselves) or a genoio.BgzfSpan (members still deflated) -> text slot `slot`"""
-        if hasattr(block, "tab"):
-            in_off, in_len, out_len, crc = block.tab
-            vp = lambda a: C.c_void_p(a.ctypes.data if a.size else 0)           # noqa: E731
-            comp = np.frombuffer(block.comp, dtype=np.uint8)
-            check(self._L.pg_vcf_dev_submit_bgzf(self._h, int(slot), vp(comp), comp.size, vp(in_off), vp(in_len), vp(out_len), vp(crc), len(in_off),
-                                                 block.head, len(block.head), len(block), len(block.first_line) + 1, 1))
+        if devroute.is_span(block):
+            args, comp = devroute.span_args(block)
+            check(self._L.pg_vcf_dev_submit_bgzf(self._h, int(slot), *args, len(block.first_line) + 1, 1))
             return comp
         if file is not None:
             check(self._L.pg_vcf_dev_submit(self._h, int(slot), None, int(file[0]), int(file[1]), len(block)))

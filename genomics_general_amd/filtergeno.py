@@ -12,15 +12,13 @@ they lie (k_deflate).
 import argparse
 import ctypes as C
 import os
-import queue
 import string
 import sys
-import threading
 import time
 
 import numpy as np
 
-from . import _lib, dist, genoio
+from . import _lib, devroute, dist, genoio
 
 IN_FMT = {"phased": 0, "diplo": 1, "alleles": 2}
 OUT_FMT = {"phased": 0, "diplo": 1, "bases": 2, "alleles": 3, "randomAllele": 4, "coded": 5, "count": 6}
@@ -149,36 +147,19 @@ def host_filter(plan, text, first_line, n_threads=0):
     return rows, err_code.value, err_line.value
 
 
-class _Device:
-    """the device route: blocks into the tokenizer's two text slots, one filtered while the next is submitted.  A block is text, or a
-    genoio.BgzfSpan whose members cross PCIe deflated (k_inflate writes the text into the slot); gz_rows: the rows leave the device as
+class _Device(devroute.SlotDevice):
+    """the device route (devroute.SlotDevice): one block filtered while the next is submitted; gz_rows: the rows leave the device as
     BGZF members (k_deflate)"""
 
     def __init__(self, plan, device, gz_rows=False):
-        from .engine import Engine
-        self.eng = Engine(device)
-        self.L = _lib.lib()
+        super().__init__(device)
         taken = C.c_int()
         _lib.check(self.L.pg_filter_dev_config(self.eng._h, *plan.args(), C.byref(taken)))
         self.taken = bool(taken.value)
         _lib.check(self.L.pg_filter_dev_set_output(self.eng._h, int(bool(gz_rows))))
-        self.slot = 0
 
     def submit(self, block, first_line):
-        s = self.slot
-        self.slot ^= 1
-        if isinstance(block, genoio.BgzfSpan):
-            in_off, in_len, out_len, crc = block.tab
-            vp = lambda a: C.c_void_p(a.ctypes.data if a.size else 0)           # noqa: E731
-            comp = np.frombuffer(block.comp, dtype=np.uint8)
-            _lib.check(self.L.pg_filter_dev_submit_bgzf(self.eng._h, s, vp(comp), comp.size, vp(in_off), vp(in_len), vp(out_len), vp(crc),
-                                                        len(in_off), bytes(block.head), len(block.head), len(block), first_line))
-            keep = (block, comp)
-        else:
-            keep = block if isinstance(block, bytes) else bytes(block)
-            _lib.check(self.L.pg_filter_dev_submit(self.eng._h, s, keep, len(keep), first_line))
-        _lib.check(self.L.pg_filter_dev_parse(self.eng._h, s))
-        return (s, keep)
+        return self._submit(block, self.L.pg_filter_dev_submit, self.L.pg_filter_dev_submit_bgzf, self.L.pg_filter_dev_parse, first_line)
 
     def collect(self, ticket):
         """(rows, members, text, lines): the rows as text or as BGZF members; rows and members None: the block is the host's, `text` its
@@ -189,86 +170,15 @@ class _Device:
         if hl.value >= 0:
             if isinstance(keep, bytes):
                 return None, None, keep, nl.value
-            n = len(keep[0])
-            text = np.empty(n, dtype=np.uint8)
-            _lib.check(self.L.pg_filter_dev_text(self.eng._h, s, text.ctypes.data_as(C.c_void_p), n))
-            return None, None, text.tobytes(), nl.value
+            return None, None, devroute.fetch(self.L.pg_filter_dev_text, self.eng._h, len(keep[0]), s).tobytes(), nl.value
         if bl.value:
-            m = np.empty(bl.value, dtype=np.uint8)
-            _lib.check(self.L.pg_filter_dev_rows_bgzf(self.eng._h, s, m.ctypes.data_as(C.c_void_p), bl.value))
-            return None, (m.tobytes(), nr.value), None, nl.value
-        out = np.empty(rl.value, dtype=np.uint8)
-        _lib.check(self.L.pg_filter_dev_rows(self.eng._h, s, out.ctypes.data_as(C.c_void_p), rl.value))
-        return out.tobytes(), None, None, nl.value
-
-    def pinned(self):
-        return self.eng.pinned.empty
+            return None, (devroute.fetch(self.L.pg_filter_dev_rows_bgzf, self.eng._h, bl.value, s).tobytes(), nr.value), None, nl.value
+        return devroute.fetch(self.L.pg_filter_dev_rows, self.eng._h, rl.value, s).tobytes(), None, None, nl.value
 
     def stats(self):
         b, h = C.c_int64(), C.c_int64()
         _lib.check(self.L.pg_filter_dev_stats(self.eng._h, C.byref(b), C.byref(h)))
         return b.value, h.value
-
-    def close(self):
-        self.eng.close()
-
-
-def _blocks(reader, block_bytes, spans, info):
-    """the input in blocks of whole lines: bytes, or -- spans: a bgzipped input the device takes as it is -- genoio.BgzfSpan (members
-    still deflated, inflated on the device into the filter's own text slot); an empty block at the end"""
-    if spans:
-        reader.spans = True
-        reader.f.alloc = spans                  # (the members land in page-locked memory)
-    while True:
-        blk = reader.read_block(block_bytes)
-        if not isinstance(blk, genoio.BgzfSpan):
-            blk = bytes(blk)
-        info["text_bytes"] += len(blk)
-        yield blk
-        if not len(blk):
-            return
-
-
-def _read_ahead(blocks, depth=2):
-    """the blocks of an iterator, produced by a thread `depth` blocks ahead of the consumer (the reading and inflating of the next
-    blocks beside the filtering of this one)"""
-    q = queue.Queue(depth)
-    stop = threading.Event()
-    done = object()
-
-    def run():
-        try:
-            for body in blocks:
-                while not stop.is_set():
-                    try:
-                        q.put(body, timeout=0.1)
-                        break
-                    except queue.Full:
-                        pass
-                if stop.is_set():
-                    break
-            q.put(done)
-        except BaseException as exc:
-            q.put(exc)
-
-    th = threading.Thread(target=run, name="pg-filter-read", daemon=True)
-    th.start()
-    try:
-        while True:
-            body = q.get()
-            if isinstance(body, BaseException):
-                raise body
-            if body is done:
-                return
-            yield body
-    finally:
-        stop.set()
-        while th.is_alive():
-            try:
-                q.get_nowait()
-            except queue.Empty:
-                pass
-            th.join(0.05)
 
 
 def filter_main(argv=None):
@@ -493,7 +403,7 @@ def _run(args, reader, out, headers, samples, popNames, popDict, ploidyDict, inc
     first = 0
     carry = b""
     host_rest = False
-    blocks = _read_ahead(_blocks(reader, block_bytes, dev.pinned() if spans else None, info))
+    blocks = devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-filter-read")
     for blk in blocks:
         eof = not len(blk)
         if isinstance(blk, genoio.BgzfSpan):

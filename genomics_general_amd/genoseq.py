@@ -19,8 +19,7 @@ import time
 
 import numpy as np
 
-from . import _lib, dist, genoio, windows
-from .filtergeno import _blocks, _read_ahead
+from . import _lib, devroute, dist, genoio, windows
 
 ERRORS = {
     1: "the line has fewer fields than the header (the reference raises on it)",
@@ -177,15 +176,11 @@ def host_seq(plan, text):
         L.pg_seq_free(C.byref(blk))
 
 
-class Device:
-    """the device route: blocks into the tokenizer's two text slots, one transposed while the next is submitted.  A block is text, or a
-    genoio.BgzfSpan whose members cross PCIe deflated (k_inflate writes the text into the slot)"""
+class Device(devroute.SlotDevice):
+    """the device route (devroute.SlotDevice): one block transposed while the next is submitted"""
 
     def __init__(self, plan, device, tile_seqs=0):
-        from .engine import Engine
-        self.eng = Engine(device)
-        self.L = _lib.lib()
-        self.slot = 0
+        super().__init__(device)
         self.configure(plan, tile_seqs)
 
     def configure(self, plan, tile_seqs=0):
@@ -197,24 +192,11 @@ class Device:
         self.taken = bool(taken.value)
 
     def submit(self, block):
-        s = self.slot
-        self.slot ^= 1
-        if isinstance(block, genoio.BgzfSpan):
-            in_off, in_len, out_len, crc = block.tab
-            vp = lambda a: C.c_void_p(a.ctypes.data if a.size else 0)           # noqa: E731
-            comp = np.frombuffer(block.comp, dtype=np.uint8)
-            _lib.check(self.L.pg_seq_dev_submit_bgzf(self.eng._h, s, vp(comp), comp.size, vp(in_off), vp(in_len), vp(out_len), vp(crc),
-                                                     len(in_off), bytes(block.head), len(block.head), len(block)))
-            keep = (block, comp)
-        else:
-            keep = block if isinstance(block, bytes) else bytes(block)
-            _lib.check(self.L.pg_seq_dev_submit(self.eng._h, s, keep, len(keep)))
-        _lib.check(self.L.pg_seq_dev_parse(self.eng._h, s))
-        return (s, keep)
+        return self._submit(block, self.L.pg_seq_dev_submit, self.L.pg_seq_dev_submit_bgzf, self.L.pg_seq_dev_parse)
 
     def text(self, s, off, n):
-        out = np.empty(max(n, 1), dtype=np.uint8)[:n]
-        _lib.check(self.L.pg_seq_dev_text(self.eng._h, s, off, n, out.ctypes.data_as(C.c_void_p)))
+        out = np.empty(max(n, 1), dtype=np.uint8)[:n]               # (pg_seq_dev_text takes the length in front of the destination)
+        _lib.check(self.L.pg_seq_dev_text(self.eng._h, s, off, n, C.c_void_p(out.ctypes.data)))
         return out.tobytes()
 
     def collect(self, ticket, padded=False):
@@ -249,16 +231,10 @@ class Device:
             names.append(piece[:piece.index(b"\t")].decode("ascii"))
         return Chunk(n, mat=mat, stride=1), pos, starts, names, None, nl.value
 
-    def pinned(self):
-        return self.eng.pinned.empty
-
     def stats(self):
         b, h, lm, tm = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
         _lib.check(self.L.pg_seq_dev_stats(self.eng._h, C.byref(b), C.byref(h), C.byref(lm), C.byref(tm)))
         return b.value, h.value, lm.value, tm.value
-
-    def close(self):
-        self.eng.close()
 
 
 class Sites:
@@ -475,7 +451,7 @@ def main(argv=None):
     try:
         spans = (dev is not None and isinstance(getattr(reader, "f", None), genoio.BgzfFile) and os.environ.get("PG_BGZF_DEVICE", "1") != "0")
         pending = None
-        for blk in _read_ahead(_blocks(reader, block_bytes, dev.pinned() if spans else None, info)):
+        for blk in devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-seq-read"):
             if not len(blk):
                 break
             info["blocks"] += 1

@@ -22,8 +22,7 @@ import time
 
 import numpy as np
 
-from . import _lib, dist, genoio
-from .filtergeno import _blocks
+from . import _lib, devroute, dist, genoio
 
 MAX_FILES = 32
 METHODS = {"intersect": 0, "union": 1, "all": 2}
@@ -174,11 +173,8 @@ class Device:
 
     def submit(self, f, block):
         if isinstance(block, genoio.BgzfSpan):
-            in_off, in_len, out_len, crc = block.tab
-            vp = lambda a: C.c_void_p(a.ctypes.data if a.size else 0)           # noqa: E731
-            comp = np.frombuffer(block.comp, dtype=np.uint8)
-            _lib.check(self.L.pg_merge_dev_submit_bgzf(self.eng._h, f, vp(comp), comp.size, vp(in_off), vp(in_len), vp(out_len), vp(crc),
-                                                       len(in_off), bytes(block.head), len(block.head), len(block)))
+            args, _comp = devroute.span_args(block)
+            _lib.check(self.L.pg_merge_dev_submit_bgzf(self.eng._h, f, *args))
         else:
             _lib.check(self.L.pg_merge_dev_submit(self.eng._h, f, block, len(block)))
 
@@ -195,8 +191,7 @@ class Device:
                                              C.byref(nz)))
         bgzf = bool(self.gz_rows and nz.value)
         n = nz.value if bgzf else nb.value
-        out = np.empty(max(n, 1), dtype=np.uint8)[:n]
-        _lib.check(self.L.pg_merge_dev_rows(self.eng._h, int(bgzf), out.ctypes.data, n))
+        out = devroute.fetch(self.L.pg_merge_dev_rows, self.eng._h, n, int(bgzf))
         return (None, out.tobytes(), nr.value, done) if bgzf else (out.tobytes(), None, nr.value, done)
 
     def advance(self, done, prevs):
@@ -206,9 +201,7 @@ class Device:
         _lib.check(self.L.pg_merge_dev_advance(self.eng._h, done.ctypes.data, ps.ctypes.data, pp.ctypes.data))
 
     def text(self, f, n):
-        out = np.empty(max(n, 1), dtype=np.uint8)[:n]
-        _lib.check(self.L.pg_merge_dev_text(self.eng._h, f, out.ctypes.data, n))
-        return out.tobytes()
+        return devroute.fetch(self.L.pg_merge_dev_text, self.eng._h, n, f).tobytes()
 
     def pinned(self):
         return self.eng.pinned.empty
@@ -309,7 +302,7 @@ def main(argv=None):
         spans_ok = dev is not None and os.environ.get("PG_BGZF_DEVICE", "1") != "0"
         for f in files:
             spans = spans_ok and isinstance(getattr(f.reader, "f", None), genoio.BgzfFile)
-            f.blocks = _blocks(f.reader, share, dev.pinned() if spans else None, info)
+            f.blocks = devroute.blocks(f.reader, share, dev.pinned() if spans else None, info)
 
         def to_host():
             """the rest of the job is the host route's (a carriage return: the reference's text mode ends a line there)"""

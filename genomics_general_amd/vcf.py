@@ -27,7 +27,7 @@ import time
 
 import numpy as np
 
-from . import _lib, genoio
+from . import _lib, devroute, genoio
 from ._lib import check
 
 SITE_TYPES = {"MONO": 1, "SNP": 2, "INDEL": 4}
@@ -214,42 +214,6 @@ def _text_blocks(reader, block_bytes, n_threads=0, plan=None, gz_rows=False):
             maker.join()
         _text_blocks.last_info = info             # (the engine lives on: the parser may still be reading the last block in its memory)
         _text_blocks.engine = made.get("engine")
-
-
-def _read_ahead(blocks, depth=2):
-    """the blocks of an iterator, produced by a thread `depth` blocks ahead of the consumer"""
-    q = queue.Queue(depth)
-    stop = threading.Event()
-    done = object()
-
-    def run():
-        try:
-            for body in blocks:
-                q.put(body)
-                if stop.is_set():
-                    break
-            q.put(done)
-        except BaseException as exc:
-            q.put(exc)
-
-    th = threading.Thread(target=run, name="pg-vcf-read", daemon=True)
-    th.start()
-    try:
-        while True:
-            body = q.get()
-            if isinstance(body, BaseException):
-                raise body
-            if body is done:
-                return
-            yield body
-    finally:
-        stop.set()
-        while th.is_alive():                                  # a reader blocked on a full queue
-            try:
-                q.get_nowait()
-            except queue.Empty:
-                pass
-            th.join(0.05)
 
 
 def _last_key(body):
@@ -806,7 +770,7 @@ def parse_vcf_main(argv=None):
     t0 = time.perf_counter()
     pending, slot = None, 0
     try:
-        for body, where in _read_ahead(_text_blocks(reader, block_bytes, int(args.threads), dev_plan, gz_rows)):
+        for body, where in devroute.read_ahead(_text_blocks(reader, block_bytes, int(args.threads), dev_plan, gz_rows), "pg-vcf-read"):
             t0 = lap("wait_for_block_s", t0)
             if where is None:
                 if pending is not None:

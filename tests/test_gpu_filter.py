@@ -129,3 +129,31 @@ def test_irregular_line_hands_its_block_to_the_host(tmp_path):
     got, info = _run(inp, argv, str(tmp_path / "d.geno"), block=4000)
     assert got == want
     assert int(info["device_host_blocks"]) >= 1 and int(info["device_blocks"]) > int(info["device_host_blocks"]), info
+
+
+@pytest.mark.parametrize("final_newline", [False, True])
+def test_bgzf_input_whose_last_line_has_no_line_feed(final_newline, tmp_path):
+    """four data lines in two BGZF members (the header and two lines, then two lines), the last line without its line feed: through the
+    device route with the members inflated on the device, the rows are the host route's byte for byte and the unfinished line's block is
+    the host's; with the line feed restored no block is.  (Whether a block of members ends in a line feed is read on the device once its
+    line feeds are counted: pg_line_slot.h's tail_unknown)"""
+    from genomics_general_amd import genoio
+    head = "#CHROM\tPOS\ta\tb\tc\n"
+    lines = ["c1\t%d\t%s\n" % (i + 1, cells) for i, cells in enumerate(("A/A\tA/T\tT/T", "A/A\tA/A\tA/A", "C/C\tC/G\tN/N", "G/T\tT/T\tG/G"))]
+    text = (head + "".join(lines)).encode()
+    if not final_newline:
+        text = text[:-1]
+    inp = str(tmp_path / "in.geno.gz")
+    bz = genoio.bgzf_compress(text, block=len(head + lines[0] + lines[1]))
+    assert len(genoio.bgzf_walk(bz)[0][0]) == 3                   # (two members of text, bgzip's empty last)
+    with open(inp, "wb") as f:
+        f.write(bz)
+    argv = ["--minAlleles", "2"]
+    want, _ = _run(inp, argv, str(tmp_path / "h.geno"), device=False)
+    got, info = _run(inp, argv, str(tmp_path / "d.geno"))
+    assert got == want and got.count(b"\n") == 4                  # (the header and lines 1, 3, 4: the host route ends the last line itself)
+    assert int(info["blocks_inflated_on_device"]) >= 1 and int(info["device_blocks"]) >= 1, info
+    if final_newline:
+        assert int(info["device_host_blocks"]) == 0, info
+    else:
+        assert int(info["device_host_blocks"]) >= 1, info

@@ -112,3 +112,50 @@ def test_seq_irregular_line_goes_to_the_host_route(device, tmp_path, monkeypatch
     rc, host_out, err = run_main(argv)
     assert rc == 0 and dev_out == host_out
     assert [ln.split(b"   ")[1] for ln in host_out.splitlines()[1:]] == [bytes(r) for r in numpy_matrix(sites, sel, True, False)]
+
+
+@pytest.mark.parametrize("final_newline", [False, True])
+def test_seq_bgzf_input_whose_last_line_has_no_line_feed(final_newline, device, tmp_path, monkeypatch):
+    """four data lines in two BGZF members (the header and two lines, then two lines), the last line without its line feed: through the
+    device route with the members inflated on the device, the output is the host route's byte for byte and the unfinished line's block
+    is the host's; with the line feed restored no block is.  Then the same lines as ONE block of members handed to the device as it
+    is: whether it ends in a line feed is read on the device once its line feeds are counted (pg_line_slot.h's tail_unknown), and
+    without one the block comes back as the host's, its text with it"""
+    ploidies = [2, 2, 1]
+    header, text, sites = random_geno(17, 4, ploidies)
+    lines = text.splitlines(keepends=True)
+    whole = (header + text).encode()
+    if not final_newline:
+        whole = whole[:-1]
+    inp = str(tmp_path / "in.geno.gz")
+    bz = genoio.bgzf_compress(whole, block=len(header + lines[0] + lines[1]))
+    assert len(genoio.bgzf_walk(bz)[0][0]) == 3                   # (two members of text, bgzip's empty last)
+    with open(inp, "wb") as f:
+        f.write(bz)
+    argv = ["-g", inp, "--splitPhased", "--ploidy"] + [str(p) for p in ploidies] + ["-f", "fasta"]
+    rc, dev_out, err = run_main(argv)
+    assert rc == 0, err
+    info = dict(genoseq.last_info)
+    monkeypatch.setenv("PG_SEQ_DEVICE", "0")
+    rc, host_out, err = run_main(argv)
+    assert rc == 0 and dev_out == host_out and len(host_out) > 0
+    assert info["blocks_inflated_on_device"] >= 1 and info["device_blocks"] >= 1, info
+    if final_newline:
+        assert info["device_host_blocks"] == 0, info
+    else:
+        assert info["device_host_blocks"] >= 1, info
+    # one block of members, as genoio.BgzfFile.read_span would hand it out if it did not cut behind the last line feed
+    body = whole[len(header):]
+    bz = genoio.bgzf_compress(body, block=(len(body) + 1) // 2)
+    tab, used, n_text = genoio.bgzf_walk(bz)
+    assert n_text == len(body) and len(tab[0]) == 3
+    comp = np.frombuffer(bz, dtype=np.uint8)[:used]
+    sel = [(c, 2 * h) for c, p in enumerate(ploidies) for h in range(p)]
+    device.configure(plan_for(header, ploidies, sel, False), 0)
+    before = device.stats()[1]
+    chunk, pos, _, _, text_back, line = device.collect(device.submit(genoio.BgzfSpan(b"", comp, tab, n_text, lines[0].encode()[:-1])))
+    if final_newline:
+        assert chunk is not None and np.array_equal(chunk.mat, numpy_matrix(sites, sel, True, False)) and device.stats()[1] == before
+        assert [int(p) for p in pos] == [p for _, p, _ in sites]
+    else:
+        assert chunk is None and line == 0 and text_back == body and device.stats()[1] == before + 1
