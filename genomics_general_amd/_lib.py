@@ -126,6 +126,23 @@ SIGNATURES = {
     "pg_filter_dev_rows_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
     "pg_filter_dev_text": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
     "pg_filter_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_gvcf_ref_table": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32]),
+    "pg_gvcf_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                               C.c_int32, C.c_void_p, C.c_char_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                               C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    "pg_gvcf_dev_config": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int)]),
+    "pg_gvcf_dev_submit": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int64]),
+    "pg_gvcf_dev_submit_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                          C.c_char_p, C.c_int64, C.c_int64]),
+    "pg_gvcf_dev_set_output": (C.c_int, [_P, C.c_int]),
+    "pg_gvcf_dev_parse": (C.c_int, [_P, C.c_int]),
+    "pg_gvcf_dev_collect": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_gvcf_dev_rows": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
+    "pg_gvcf_dev_rows_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
+    "pg_gvcf_dev_text": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
+    "pg_gvcf_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pg_seq_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]),
     "pg_seq_free": (None, [C.c_void_p]),
     "pg_seq_dev_config": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

@@ -218,6 +218,12 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
         F.flags.release(); F.out.release(); F.rlen.release(); F.roff.release(); F.pos.release(); F.status.release(); F.h_status.release(); F.df.release();
         if (F.done) (void)hipEventDestroy(F.done);
     }
+    c->gvcf.sel_col.release(); c->gvcf.table.release(); c->gvcf.names.release(); c->gvcf.seq.release(); c->gvcf.name_off.release(); c->gvcf.seq_len.release(); c->gvcf.seq_off.release();
+    for (int k = 0; k < 2; ++k) {
+        pg_ctx::GvcfDev::Slot &G = c->gvcf.s[k];
+        G.out.release(); G.rlen.release(); G.roff.release(); G.status.release(); G.h_status.release(); G.df.release();
+        if (G.done) (void)hipEventDestroy(G.done);
+    }
     c->seq.sel_col.release(); c->seq.sel_off.release(); c->seq.sel_len.release();
     for (int k = 0; k < 2; ++k) {
         pg_ctx::SeqDev::Slot &Q = c->seq.s[k];

@@ -213,6 +213,26 @@ struct pg_ctx {
         bool bgzf_rows = false;
         int64_t blocks = 0, host_blocks = 0;
     } filt;
+    // .geno sites written as VCF rows on the device (pg_gvcf_dev.hip): the option set, the fasta (names, their table, the sequences
+    // side by side) and, per text slot of the tokenizer, the row sizes and places, the rows
+    struct GvcfDev {
+        bool configured = false;
+        pg_gvcf_cfg cfg;
+        DevBuf<int32_t> sel_col, table;
+        DevBuf<uint8_t> names, seq;
+        DevBuf<int64_t> name_off, seq_len, seq_off;
+        uint32_t mask = 0;
+        int32_t n_seq = 0;
+        struct Slot : LineSlot {
+            DevBuf<uint8_t> out;
+            DevBuf<uint32_t> rlen;
+            DevBuf<int64_t> roff;
+            Deflate df;                                    // the rows deflated where they lie (pg_gvcf_dev_set_output)
+            int64_t out_cap = 0;
+        } s[2];
+        bool bgzf_rows = false;
+        int64_t blocks = 0, host_blocks = 0;
+    } gvcf;
     // .geno lines turned into sequences on the device (pg_seq_dev.hip): the option set, the selection tables and, per text slot of the
     // tokenizer, the lines' records, the kept lines' places, the sites' records and the matrix [n_seq][pitch]
     struct SeqDev {

@@ -13,6 +13,7 @@
 // regular spelling, or one on which the reference raises, hands the BLOCK to the host route (pg_filter_dev_collect reports the line).
 #include "pg_ctx.h"
 #include "pg_filter_core.h"
+#include "pg_line_fields.h"
 #include "pg_wave.h"
 
 #include <algorithm>
@@ -45,12 +46,6 @@ struct FiltArgs {
     uint8_t *out;
     long long *status;
 };
-
-// the cell of field c: [s, e) within the line, from the tab table
-__device__ inline void field_at(const uint32_t *tabs, int c, int n_cols, uint32_t n, uint32_t *s, uint32_t *e) {
-    *s = c ? tabs[c - 1] + 1 : 0;
-    *e = c < n_cols - 1 ? tabs[c] : n;
-}
 
 // the cells of the selected columns classified and summed: tot over the wave (the same on every lane), the populations' sums in LDS
 // (`pop`, n_pops records behind the tab table, added by LDS atomics: no per-lane array).  Returns false (on every lane) when some cell
@@ -91,34 +86,6 @@ __device__ bool line_sums(const FiltArgs &A, const PgfConfig &cfg, const uint8_t
     tot->hets = pg_wave_sum(t.hets);
     tot->not_nn = pg_wave_sum(t.not_nn);
     return true;
-}
-
-// the line's tabs into LDS; false when the line is not of the regular spelling (the host's then)
-__device__ bool line_tabs(const uint8_t *line, uint32_t n, int n_cols, int lane, uint32_t *tabs) {
-    uint32_t ntab = 0;
-    bool irr = n == 0;
-    for (uint32_t base = 0; base < n; base += 64) {
-        const uint32_t k = base + (uint32_t)lane;
-        const uint8_t b = k < n ? line[k] : (uint8_t)'x';
-        const bool tab = k < n && b == '\t';
-        const bool odd = k < n && (b == ' ' || b == '\v' || b == '\f' || b == '\r' || (b >= 0x1c && b <= 0x1f) || b >= 0x80);
-        const uint64_t m = __ballot(tab);
-        if (tab) {
-            const uint32_t idx = ntab + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (idx < (uint32_t)(n_cols - 1)) tabs[idx] = k;
-        }
-        ntab += (uint32_t)__popcll(m);
-        irr = irr || __ballot(odd) != 0;
-    }
-    if (irr || ntab != (uint32_t)(n_cols - 1)) return false;
-    __syncthreads();
-    bool empty = false;
-    for (int c = lane; c < n_cols; c += 64) {
-        uint32_t s, e;
-        field_at(tabs, c, n_cols, n, &s, &e);
-        empty = empty || e <= s;
-    }
-    return __ballot(empty) == 0;
 }
 
 // one row's size / its text

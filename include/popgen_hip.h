@@ -674,6 +674,57 @@ int pg_filter_dev_rows_bgzf(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
 int pg_filter_dev_text(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
 int pg_filter_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
 
+/* ---- `.geno` sites written as VCF rows (the genoToVCF.py drop-in, genomics_general_amd/genovcf.py) ---------------------------------
+ * Replaces makeVCFline and the per-site loop of VCF_processing/genoToVCF.py:5-21, 86-90 with parseGenoLine (genomics.py:1884-1902),
+ * Genotype / asCoded (317-365) and GenomeSite.alleles / asList("coded") (531-557).  The per-site and per-cell rules are
+ * csrc/pg_gvcf_core.h.  The option set: */
+typedef struct pg_gvcf_cfg {
+    int32_t in_fmt;                                          /* -f 0 phased 1 diplo 2 pairs */
+    int32_t n_sel;                                           /* output columns (-s, a name given twice counts twice) */
+    int32_t n_cols;                                          /* fields of the header line */
+    int32_t has_ref;                                         /* -r with at least one sequence */
+    int32_t universal_newlines;                              /* 1: a file read in text mode; 0: stdin, where \r is whitespace */
+} pg_gvcf_cfg;
+/* The tables beside it: sel_col[n_sel] the header field of each output column (a name the header holds twice: its last field),
+ * prev_same[n_cols] the field before with the same name or -1 (a line too short for the last one takes that: dict(zip(names, cells)));
+ * the fasta (genoToVCF.py:55-56, parseFasta genomics.py:2256-2261) as n_seq names side by side (ref_names, name_off[n_seq + 1]), their
+ * lengths seq_len[n_seq], where each begins in seq (seq_off[n_seq]) and an open-addressed table over the names (pg_gvcf_ref_table:
+ * table[mask + 1], mask + 1 a power of two >= 2 n_seq and >= 4).
+ *
+ * Host route, every spelling line.split() takes: text[0 .. len) holds lines behind the header ('#' lines are skipped); the rows ->
+ * out[0 .. out_cap) when they fit; *rows_len_out their bytes either way (3 len + 40 per line + 64 always fit).  A line on which the
+ * reference dies: *err_line_out its index in the block, *err_code_out the PGG_E_* code (pg_gvcf_core.h), the rows before it written;
+ * else -1 / 0. */
+int pg_gvcf_ref_table(const char *ref_names, const int64_t *name_off, int32_t n_seq, int32_t *table, uint32_t mask);
+int pg_gvcf_text(const pg_gvcf_cfg *cfg, const int32_t *sel_col, const int32_t *prev_same, const char *ref_names, const int64_t *name_off,
+                 const int64_t *seq_len, const int64_t *seq_off, const int32_t *table, uint32_t mask, int32_t n_seq, const uint8_t *seq,
+                 const char *text, int64_t len, int n_threads, char *out, int64_t out_cap, int64_t *rows_len_out, int64_t *n_rows_out,
+                 int64_t *err_line_out, int *err_code_out);
+/* Device route (csrc/pg_gvcf_dev.hip) for the regular spelling (fields split by single tabs, the header's field count, ASCII, a
+ * position of digits only), the calls of the filter route's slot protocol (csrc/pg_line_slot.h):
+ *   pg_gvcf_dev_config        the option set and the fasta, uploaded once; *taken_out = 0 when the device does not take the run (a
+ *                             header too wide for the tab table in LDS, no output column), -1 when the sequences exceed the scratch
+ *                             budget (PG_SCRATCH_GIB)
+ *   pg_gvcf_dev_submit / _submit_bgzf / _set_output / _parse / _collect / _rows / _rows_bgzf / _text / _stats
+ *                             as pg_filter_dev_*: k_gvcf_lines<0> sizes the rows, a scan places them, k_gvcf_lines<1> writes them
+ *                             (and k_deflate makes them BGZF members); a line the device does not take hands the block to
+ *                             pg_gvcf_text */
+int pg_gvcf_dev_config(pg_ctx *ctx, const pg_gvcf_cfg *cfg, const int32_t *sel_col, const char *ref_names, const int64_t *name_off,
+                       const int64_t *seq_len, const int64_t *seq_off, const int32_t *table, uint32_t mask, int32_t n_seq, const uint8_t *seq,
+                       int64_t seq_bytes, int *taken_out);
+int pg_gvcf_dev_submit(pg_ctx *ctx, int slot, const char *text, int64_t len);
+int pg_gvcf_dev_submit_bgzf(pg_ctx *ctx, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                            const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                            int64_t text_len);
+int pg_gvcf_dev_set_output(pg_ctx *ctx, int bgzf_members);
+int pg_gvcf_dev_parse(pg_ctx *ctx, int slot);
+int pg_gvcf_dev_collect(pg_ctx *ctx, int slot, int64_t *rows_len_out, int64_t *n_rows_out, int64_t *host_line_out, int64_t *bgzf_len_out,
+                        int64_t *n_lines_out);
+int pg_gvcf_dev_rows(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
+int pg_gvcf_dev_rows_bgzf(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
+int pg_gvcf_dev_text(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
+int pg_gvcf_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
+
 /* ---- `.geno` lines turned into sequences (the genoToSeq.py drop-in, genomics_general_amd/genoseq.py) -----------------------------
  * Replaces the per-site loop of genoToSeq.py: parseGenoLine (genomics.py:1884-1902), GenoWindow.addSite / seqDict (1753-1793) and the
  * join of makeAlnString (2232-2251) -- a byte transpose, site-major text in, sequence-major bytes out.  The per-line and per-cell rules
