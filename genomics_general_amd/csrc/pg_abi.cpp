@@ -224,6 +224,12 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
         G.out.release(); G.rlen.release(); G.roff.release(); G.status.release(); G.h_status.release(); G.df.release();
         if (G.done) (void)hipEventDestroy(G.done);
     }
+    c->eig.sel_col.release(); c->eig.table.release(); c->eig.names.release(); c->eig.labels.release(); c->eig.name_off.release(); c->eig.label_off.release();
+    for (int k = 0; k < 2; ++k) {
+        pg_ctx::EigDev::Slot &E = c->eig.s[k];
+        E.snp.release(); E.geno.release(); E.site.release(); E.rlen.release(); E.entry.release(); E.roff.release(); E.rank.release(); E.status.release(); E.h_status.release();
+        if (E.done) (void)hipEventDestroy(E.done);
+    }
     c->seq.sel_col.release(); c->seq.sel_off.release(); c->seq.sel_len.release();
     for (int k = 0; k < 2; ++k) {
         pg_ctx::SeqDev::Slot &Q = c->seq.s[k];

@@ -233,6 +233,25 @@ struct pg_ctx {
         bool bgzf_rows = false;
         int64_t blocks = 0, host_blocks = 0;
     } gvcf;
+    // biallelic .geno sites written as EIGENSTRAT rows on the device (pg_eig_dev.hip): the option set, the --chromFile (scaffold names,
+    // their table, the labels side by side) and, per text slot of the tokenizer, what the first run leaves per line (the .snp row's
+    // size, the site's alleles, the label's entry), the kept lines' ranks and places, the two outputs
+    struct EigDev {
+        bool configured = false;
+        pg_eig_cfg cfg;
+        DevBuf<int32_t> sel_col, table;
+        DevBuf<uint8_t> names, labels;
+        DevBuf<int64_t> name_off, label_off;
+        uint32_t mask = 0;
+        struct Slot : LineSlot {
+            DevBuf<uint8_t> snp, geno, site;
+            DevBuf<uint32_t> rlen;
+            DevBuf<int32_t> entry;
+            DevBuf<int64_t> roff, rank;
+            int64_t snp_cap = 0, first_site = 0;
+        } s[2];
+        int64_t blocks = 0, host_blocks = 0;
+    } eig;
     // .geno lines turned into sequences on the device (pg_seq_dev.hip): the option set, the selection tables and, per text slot of the
     // tokenizer, the lines' records, the kept lines' places, the sites' records and the matrix [n_seq][pitch]
     struct SeqDev {

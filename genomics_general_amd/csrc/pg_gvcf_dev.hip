@@ -41,22 +41,6 @@ struct GvcfArgs {
     long long *status;
 };
 
-// the scaffold of the line (its first t0 bytes) in the fasta, -1 when it is not there; the same on every lane
-__device__ int32_t line_scaffold(const pgm_fai &F, const uint8_t *line, uint32_t t0, int lane) {
-    uint32_t sum = 0;
-    for (uint32_t k = (uint32_t)lane; k < t0; k += 64) sum += pgm_hash_byte(line[k], k);
-    sum = pg_wave_sum(sum);
-    for (uint32_t at = pgm_hash_end(sum, t0) & F.mask;; at = (at + 1) & F.mask) {
-        const int32_t e = F.table[at];
-        if (e < 0) return -1;
-        const int64_t a = F.name_off[e];
-        if (F.name_off[e + 1] - a != (int64_t)t0) continue;
-        bool differ = false;
-        for (uint32_t k = (uint32_t)lane; k < t0; k += 64) differ = differ || F.names[a + k] != line[k];
-        if (__ballot(differ) == 0) return e;
-    }
-}
-
 // one row's size / its text
 template <int RENDER>
 __global__ __launch_bounds__(64) void k_gvcf_lines(GvcfArgs A, PggConfig cfg) {

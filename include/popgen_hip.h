@@ -725,6 +725,67 @@ int pg_gvcf_dev_rows_bgzf(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
 int pg_gvcf_dev_text(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
 int pg_gvcf_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
 
+/* ---- biallelic `.geno` sites written as EIGENSTRAT rows (the genoToEigenstrat.py drop-in, genomics_general_amd/genoeig.py) --------
+ * Replaces the per-site loop of tools/genoToEigenstrat.py:48-73 with parseGenoLine (genomics.py:1884-1902), Genotype / asCount
+ * (317-370) and GenomeSite.alleles / asList("count") (535-557).  The per-site and per-cell rules are csrc/pg_eig_core.h.  The option
+ * set: */
+typedef struct pg_eig_cfg {
+    int32_t in_fmt;                                          /* -f 0 phased 1 diplo */
+    int32_t n_sel;                                           /* written columns (-s; a header name given twice counts twice) */
+    int32_t n_cols;                                          /* fields of the header line */
+    int32_t universal_newlines;                              /* 1: a file read in text mode; 0: stdin, where \r is whitespace */
+    int32_t cumulative;                                      /* --cumulativePos */
+    int32_t n_scaf;                                          /* scaffolds of the --chromFile */
+} pg_eig_cfg;
+/* what one block hands the next */
+typedef struct pg_eig_state {
+    int64_t sites;                                           /* sites in front of the block (the .snp row's index) */
+    int64_t pos;                                             /* --cumulativePos: the last written position */
+    int64_t scaf_len;                                        /*   bytes of the last kept site's scaffold in scaf_io, -1: none yet */
+    int32_t entry;                                           /*   its label's entry, -1: none yet */
+    int32_t pad;
+} pg_eig_state;
+/* The tables beside them: sel_col[n_sel] the header field of each written column (a name the header holds twice: its last field),
+ * prev_same / next_same[n_cols] the field before / behind with the same name or -1 (dict(zip(names, cells)): of a repeated name the
+ * last cell the line has counts, once), both NULL for a header without repeats; the --chromFile as n_scaf scaffold names side by side
+ * (names, name_off[n_scaf + 1]) under an open-addressed table (pg_gvcf_ref_table), their labels side by side (labels,
+ * label_off[n_scaf + 2]: entry n_scaf is str(nullChrom), every other scaffold's label); with --cumulativePos label_key[n_scaf + 1]
+ * the slot of each entry's label in offsets[] or -1 (the reference's KeyError), offsets[] the chromosomes' offsets and scaf_io the
+ * last kept site's scaffold (room for max(len, state->scaf_len) bytes), all three carried from block to block with *state.
+ *
+ * Host route, every spelling line.split() takes: text[0 .. len) holds lines behind the header ('#' lines are no sites); the .geno
+ * rows -> geno[0 .. geno_cap), the .snp rows -> snp[0 .. snp_cap) when both fit (then *state moves on), their bytes either way.  A
+ * line on which the reference dies: *err_line_out its index in the block, *err_code_out the PGE_E_* code (pg_eig_core.h), the rows
+ * before it written; else -1 / 0.  *n_sites_out: the sites walked. */
+int pg_eig_text(const pg_eig_cfg *cfg, const int32_t *sel_col, const int32_t *prev_same, const int32_t *next_same, const char *names,
+                const int64_t *name_off, const int32_t *table, uint32_t mask, const char *labels, const int64_t *label_off,
+                const int32_t *label_key, pg_eig_state *state, int64_t *offsets, char *scaf_io, const char *text, int64_t len, int n_threads,
+                char *geno, int64_t geno_cap, char *snp, int64_t snp_cap, int64_t *geno_len_out, int64_t *snp_len_out, int64_t *n_rows_out,
+                int64_t *n_sites_out, int64_t *err_line_out, int *err_code_out);
+/* Device route (csrc/pg_eig_dev.hip) for the regular spelling (fields split by single tabs, the header's field count, ASCII, a
+ * position of digits only, cells of at most nine alleles), the calls of the slot protocol (csrc/pg_line_slot.h):
+ *   pg_eig_dev_config         the option set and the --chromFile, uploaded once; *taken_out = 0 when the device does not take the run
+ *                             (--cumulativePos, a header too wide for the tab table in LDS, no written column), -1 when the
+ *                             --chromFile exceeds PG_EIG_MAX_SCAF scaffolds or PG_EIG_MAX_LABEL bytes in a label
+ *   pg_eig_dev_submit / _submit_bgzf / _collect / _text / _stats   as pg_gvcf_dev_*
+ *   pg_eig_dev_parse          first_site: the sites in front of the block; k_eig_lines<0> counts over all columns, decides, sizes
+ *                             the .snp rows, k_eig_scan ranks and places them, k_eig_lines<1> writes both outputs; *n_lines_out the
+ *                             block's lines
+ *   pg_eig_dev_rows           which = 0 the .geno rows (n_rows (n_sel + 1) bytes), 1 the .snp rows */
+#define PG_EIG_MAX_SCAF (1 << 22)
+#define PG_EIG_MAX_LABEL 255
+int pg_eig_dev_config(pg_ctx *ctx, const pg_eig_cfg *cfg, const int32_t *sel_col, const char *names, const int64_t *name_off,
+                      const int32_t *table, uint32_t mask, const char *labels, const int64_t *label_off, int *taken_out);
+int pg_eig_dev_submit(pg_ctx *ctx, int slot, const char *text, int64_t len);
+int pg_eig_dev_submit_bgzf(pg_ctx *ctx, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                           const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                           int64_t text_len);
+int pg_eig_dev_parse(pg_ctx *ctx, int slot, int64_t first_site, int64_t *n_lines_out);
+int pg_eig_dev_collect(pg_ctx *ctx, int slot, int64_t *snp_len_out, int64_t *n_rows_out, int64_t *host_line_out, int64_t *n_lines_out);
+int pg_eig_dev_rows(pg_ctx *ctx, int slot, int which, uint8_t *dst, int64_t len);
+int pg_eig_dev_text(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
+int pg_eig_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
+
 /* ---- `.geno` lines turned into sequences (the genoToSeq.py drop-in, genomics_general_amd/genoseq.py) -----------------------------
  * Replaces the per-site loop of genoToSeq.py: parseGenoLine (genomics.py:1884-1902), GenoWindow.addSite / seqDict (1753-1793) and the
  * join of makeAlnString (2232-2251) -- a byte transpose, site-major text in, sequence-major bytes out.  The per-line and per-cell rules
