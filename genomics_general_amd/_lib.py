@@ -157,6 +157,20 @@ SIGNATURES = {
     "pg_eig_dev_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "pg_eig_dev_text": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
     "pg_eig_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_ped_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_int, C.c_void_p]),
+    "pg_ped_free": (None, [C.c_void_p]),
+    "pg_ped_dev_config": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "pg_ped_dev_submit": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int64]),
+    "pg_ped_dev_submit_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_char_p, C.c_int64, C.c_int64]),
+    "pg_ped_dev_parse": (C.c_int, [_P, C.c_int]),
+    "pg_ped_dev_collect": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64)]),
+    "pg_ped_dev_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "pg_ped_dev_meta": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p]),
+    "pg_ped_dev_text": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "pg_ped_dev_tile_seqs": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "pg_ped_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pg_seq_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_void_p]),
     "pg_seq_free": (None, [C.c_void_p]),
     "pg_seq_dev_config": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

@@ -2071,3 +2071,14 @@ def mergegeno_main(argv=None):
     (pg_merge_dev_*: the device route; pg_merge_text: the host route)."""
     from . import mergegeno
     return mergegeno.main(argv)
+
+
+# ==========================================================================================================
+# tools/genoToPlink.py  (.geno sites as PED / MAP / FAM; genomics_general_amd/genoplink.py)
+# ==========================================================================================================
+@guarded_main
+def genotoplink_main(argv=None):
+    """Drop-in for the reference's tools/genoToPlink.py (genoToPlink.py:24-79): the sites' cells are expanded into alleles and
+    transposed into PED rows by k_ped_lines / k_ped_tile, the .map rows written by k_ped_map"""
+    from . import genoplink
+    return genoplink.main(argv)

@@ -238,6 +238,13 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
         for (hipEvent_t e : {Q.done, Q.t0, Q.t1, Q.t2, Q.t3})
             if (e) (void)hipEventDestroy(e);
     }
+    c->ped.sel_col.release(); c->ped.sel_len.release(); c->ped.sel_w.release(); c->ped.sel_woff.release();
+    for (int k = 0; k < 2; ++k) {
+        pg_ctx::PedDev::Slot &P = c->ped.s[k];
+        P.keep.release(); P.rlen.release(); P.runf.release(); P.rrun.release(); P.out.release(); P.map.release(); P.row.release(); P.roff.release();
+        P.rstart.release(); P.line_of.release(); P.status.release(); P.h_status.release();
+        if (P.done) (void)hipEventDestroy(P.done);
+    }
     c->tok_pin.release();
     drop_events(c);
     c->gt.release();

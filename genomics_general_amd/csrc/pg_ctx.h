@@ -271,7 +271,25 @@ struct pg_ctx {
         double lines_ms = 0, tile_ms = 0;
         int64_t blocks = 0, host_blocks = 0;
     } seq;
-    int64_t tok_nl_fallbacks = 0;                          // deflated blocks whose line feeds were found by passes over the text after all
+    // .geno sites written as PED rows and MAP lines on the device (pg_ped_dev.hip): the option set, per sample its column, the length
+    // its cells must have, the bytes a site takes in its row (2 a_q) and their sum over the samples before; per text slot of the
+    // tokenizer the lines' records, the kept lines' places, the .map rows and the matrix (sample q's row at woff[q] x pitch)
+    struct PedDev {
+        bool configured = false;
+        pg_ped_cfg cfg;
+        int tile_seqs = 0, wmax = 0;                       // samples per tile of k_ped_tile; the widest sample's bytes a site
+        int64_t wsum = 0;                                  // bytes a site takes over all samples
+        DevBuf<int32_t> sel_col, sel_len, sel_w;
+        DevBuf<int64_t> sel_woff;
+        struct Slot : LineSlot {
+            DevBuf<uint32_t> keep, rlen;                   // per line: 1 a site, 0 a '#' line; its .map row's bytes
+            DevBuf<uint8_t> runf, rrun, out, map;          // runf / rrun: the scaffold differs from the site before, per line / per site
+            DevBuf<int64_t> row, roff, rstart, line_of;
+            int64_t pitch = 0, map_cap = 0;
+        } s[2];
+        int64_t blocks = 0, host_blocks = 0;
+    } ped;
+    int64_t tok_nl_fallbacks = 0;                         // deflated blocks whose line feeds were found by passes over the text after all
     HostPin<uint8_t> tok_pin;                              // two 4 MiB page-locked buffers per staging thread
     hipStream_t tok_st[PG_TOK_WORKERS] = {};               // one copy stream per staging thread
     hipStream_t tok_crc = nullptr;                         // k_crc32 of a deflated block, beside the tokenizer's kernels

@@ -786,6 +786,64 @@ int pg_eig_dev_rows(pg_ctx *ctx, int slot, int which, uint8_t *dst, int64_t len)
 int pg_eig_dev_text(pg_ctx *ctx, int slot, uint8_t *dst, int64_t len);
 int pg_eig_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
 
+/* ---- `.geno` sites written as PED rows and MAP lines (the genoToPlink.py drop-in, genomics_general_amd/genoplink.py) --------------
+ * Replaces tools/genoToPlink.py:36-72 -- nonOverlappingSitesWindows(windSites=inf) (genomics.py:2176-2223), seqDict (1790-1793),
+ * splitSeq (390-396) and the interleaving of its zips -- with a byte transpose in which a cell expands into its alleles, each
+ * followed by a blank.  The per-cell rules are csrc/pg_ped_core.h.  The option set: */
+typedef struct pg_ped_cfg {
+    int32_t fmt;                                             /* -f 0 phased 1 diplo 2 haplo / pairs / alleles (every character an allele) */
+    int32_t n_sel;                                           /* rows of the .ped (-s, or every sample of the header) */
+    int32_t n_cols;                                          /* fields of the header line */
+    int32_t exact_cols;                                      /* no -s: a line must hold exactly the header's cells (addSite asserts) */
+} pg_ped_cfg;
+/* What the host route makes of a block (free with pg_ped_free).  A run is a stretch of sites of one scaffold (a scaffold that comes
+ * back opens a new one; the block's first site always opens one: the driver joins it to the block before).  Sample q's bytes lie at
+ * seq[seq_off[q] .. seq_off[q + 1]): run after run, site after site, the site's alleles each followed by a blank -- as many alleles
+ * as the SHORTEST cell of that sample in that run of the block gives (run_min[r * n_sel + q] its length: zip() cuts every cell to it). */
+typedef struct pg_ped_block {
+    int64_t n_sites, n_runs, seq_bytes, map_bytes;
+    uint8_t *seq;
+    int64_t *seq_off;                                        /* n_sel + 1 */
+    int64_t *run_start;                                      /* n_runs: the run's first site in the block */
+    int64_t *run_name;                                       /* 2 n_runs: where the scaffold's name lies in the text, its length */
+    int32_t *run_min;                                        /* n_runs x n_sel */
+    uint8_t *map;                                            /* the .map rows: scaffold ' ' position " 0 " position '\n' */
+    int64_t err_line;                                        /* the line the run stops on (-1: none) ... */
+    int32_t err_code;                                        /* ... and why (PGP_E_*, pg_ped_core.h) */
+} pg_ped_block;
+/* Host route, every spelling line.split() takes, cells of any length: text[0 .. len) holds lines ended by \n behind the header ('#'
+ * lines are no sites); sel_col[n_sel] the header field of each row's sample. */
+int pg_ped_text(const pg_ped_cfg *cfg, const int32_t *sel_col, const char *text, int64_t len, int n_threads, pg_ped_block *out);
+void pg_ped_free(pg_ped_block *blk);
+/* Device route (csrc/pg_ped_dev.hip) for the regular spelling (fields split by single tabs, the header's field count, ASCII, a
+ * position of digits only) and cells of the configured lengths, the calls of the slot protocol (csrc/pg_line_slot.h):
+ *   pg_ped_dev_config         the option set and sel_len[n_sel], the length every cell of a sample must have (the file's first site
+ *                             sets it); tile_seqs: samples per tile of k_ped_tile (0: as many as the LDS holds); *taken_out = 0 when
+ *                             the device does not take the run (a cell of more than PG_PED_DEV_ALLELES alleles or of an even length
+ *                             under phased, a header too wide for the tab tables in LDS)
+ *   pg_ped_dev_submit / _submit_bgzf / _stats   as pg_eig_dev_*; pg_ped_dev_text as pg_seq_dev_text
+ *   pg_ped_dev_parse          k_ped_lines checks the lines and sizes the .map rows, two scans place the sites and the rows,
+ *                             k_ped_map writes the rows, k_ped_tile transposes
+ *   pg_ped_dev_collect        waits.  *host_line_out < 0: *n_sites_out sites, *map_len_out bytes of .map rows, the samples' bytes in
+ *                             a matrix of pitch *pitch_out sites: sample q's 2 a_q bytes a site begin at 2 (a_0 + .. + a_(q-1)) x
+ *                             pitch (pg_ped_dev_rows: which = 0 the first len bytes of the matrix, 1 the .map rows); else the block
+ *                             goes to pg_ped_text
+ *   pg_ped_dev_meta           per site of the collected block: 1 where it opens a run, where its line begins in the text */
+#define PG_PED_DEV_ALLELES 4
+int pg_ped_dev_config(pg_ctx *ctx, const pg_ped_cfg *cfg, const int32_t *sel_col, const int32_t *sel_len, int tile_seqs, int *taken_out);
+int pg_ped_dev_submit(pg_ctx *ctx, int slot, const char *text, int64_t len);
+int pg_ped_dev_submit_bgzf(pg_ctx *ctx, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                           const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                           int64_t text_len);
+int pg_ped_dev_parse(pg_ctx *ctx, int slot);
+int pg_ped_dev_collect(pg_ctx *ctx, int slot, int64_t *n_sites_out, int64_t *map_len_out, int64_t *host_line_out, int64_t *n_lines_out,
+                       int64_t *pitch_out);
+int pg_ped_dev_rows(pg_ctx *ctx, int slot, int which, uint8_t *dst, int64_t len);
+int pg_ped_dev_meta(pg_ctx *ctx, int slot, uint8_t *run_dst, int64_t *start_dst);
+int pg_ped_dev_text(pg_ctx *ctx, int slot, int64_t off, int64_t len, uint8_t *dst);
+int pg_ped_dev_tile_seqs(pg_ctx *ctx, int *tile_seqs_out);
+int pg_ped_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
+
 /* ---- `.geno` lines turned into sequences (the genoToSeq.py drop-in, genomics_general_amd/genoseq.py) -----------------------------
  * Replaces the per-site loop of genoToSeq.py: parseGenoLine (genomics.py:1884-1902), GenoWindow.addSite / seqDict (1753-1793) and the
  * join of makeAlnString (2232-2251) -- a byte transpose, site-major text in, sequence-major bytes out.  The per-line and per-cell rules
