@@ -756,11 +756,14 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
     Sink xs(make_xv_win(XV, goff, b, capg, NP, h0, nw, mismatch, has_data), nullptr, /* cell */ stage_x + lane, /* stride */ 64,
             /* burst */ PACK_FUSE_XC);
     VsCompactor<Sink> vs(xs);
-    // the rows of one word: a descriptor of its own (a part may be longer than 32-bit offsets reach); a word past the part reads as zero
-    auto word_rsrc = [&](int w) -> __amdgpu_buffer_rsrc_t {
-        const int64_t row = lo + 32ll * w;
-        const int n = w < w_end ? (int)((hi - row) < 32 ? (hi - row) : 32) : 0;
-        return group_rsrc(gt, RS, n ? row : lo, n);
+    // the rows of one word: a descriptor of its own (a part may be longer than 32-bit offsets reach), stepped from this wave's word
+    // before (PgWordWalk: two scalar adds and a clip, not a 64-bit product per word); a word past the part reads as zero
+    PgWordWalk walk;
+    walk.start((uint64_t)(uintptr_t)gt, RS, lo, hi, w_end, w_begin + wave);
+    auto next_rsrc = [&]() -> __amdgpu_buffer_rsrc_t {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<int8_t *>((uintptr_t)walk.base), 0, walk.records(RS), 0x00020000);
+        walk.advance(RS);
+        return rs;
     };
     // this wave's products: cells of tile row a[p] and tile column b[p & 1] of the word with this lane half's parity
     const int r = lane & 31, kb = lane >> 5;
@@ -781,33 +784,40 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
     // row loads of every word (measured: + 0.8 ms per north-star pass).  A poll that never succeeds ends after PACK_FUSE_SPINS
     // tries and raises PG_FLAG_FUSE_STALL: the call fails instead of the kernel hanging.
     bool stalled = false;
+    // (the first read is tested on its own: nearly every poll succeeds at once and then costs the read, a compare and a branch; the
+    // spin loop behind it exists once per poll, not unrolled, with the counter's address and the target where they were)
     auto wait_ge = [&](int *ctr, int target) {
-        for (int spins = 0; __builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < target;) {
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > PACK_FUSE_SPINS) { stalled = true; break; }
+        auto below = [&]() { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < target; };
+        if (__builtin_expect(below(), 0)) {
+            int spins = 0;
+#pragma unroll 1
+            do {
+                __builtin_amdgcn_s_sleep(1);
+                if (++spins > PACK_FUSE_SPINS) { stalled = true; break; }
+            } while (below());
         }
     };
     auto arrive = [&](int *ctr) {            // after this wave's LDS reads / writes so far
         if (lane == 0) __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
-    uint32_t dn[32];
+    // Two sets of row registers change roles from word to word: the one an iteration transposes was requested an iteration before,
+    // the other is requested now.  (One set copied into the other per word: 32 v_mov, each behind a wait for its load, so that the
+    // rows had to land inside the iteration that requested them.)
+    uint32_t da[32], db[32];
 #pragma unroll
-    for (int s = 0; s < 32; ++s) dn[s] = 0u;
+    for (int s = 0; s < 32; ++s) da[s] = db[s] = 0u;
     const RowOff ro = make_row_off(RS);
     // (a lane past the row reads past every descriptor: zeros, no branch around the loads)
     const int lane_off = has_data ? 4 * lane : 0x40000000;
-    word_load(word_rsrc(w_begin + wave), lane_off, RS, 0, ro, dn);
+    word_load(next_rsrc(), lane_off, RS, 0, ro, da);
     __syncthreads();
     int slot = 0, round8 = 0, pslot = PACK_FUSE_NB - 1, pround8 = -8;        // it % NB, 8 (it / NB); the same of it - 1
-    for (int it = 0; it < nit; ++it) {
+    // One iteration: the word in d (requested an iteration ago), the rows of this wave's next word requested into dnx.
+    auto iteration = [&](int it, const uint32_t (&d)[32], uint32_t (&dnx)[32]) __attribute__((always_inline)) {
         const int w = w_begin + 8 * it + wave;
-        uint32_t pa[4] = {0u, 0u, 0u, 0u};
-        uint32_t R[4][8];
         const bool live = w < w_end;            // wave-uniform
-        uint32_t d[32];
-#pragma unroll
-        for (int s = 0; s < 32; ++s) d[s] = dn[s];
-        word_load(word_rsrc(w + 8), lane_off, RS, 0, ro, dn);
+        uint32_t pa[4], R[4][8];
+        word_load(next_rsrc(), lane_off, RS, 0, ro, dnx);
         // K step q of the cells of the iteration before, and the transposes of sites 8q .. 8q+7: one basic block, so that the
         // matrix pipe works under this wave's own vector instructions (a word past the part and a lane past the row transpose zeros).
         // The products are issued one at a time between the three pieces of word_called_presence_keep's q (the order is pinned
@@ -851,7 +861,9 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const uint32_t t = R[q][hk] + 0x77777777u;
-                    if (DIP) bad |= t ^ (R[q][hk + 1] + 0x77777777u);
+                    // bad | (t ^ odd slot's t) in one v_bitop3_b32 (truth table 0xF0 | (0xCC ^ 0xAA)); left to itself the compiler
+                    // spends an xor per slot pair and an or3 per two of them
+                    if (DIP) bad = __builtin_amdgcn_bitop3_b32(bad, t, R[q][hk + 1] + 0x77777777u, 0xF6);
                     c[q] = (t >> 3) & 0x11111111u;
                 }
                 if (u0 + k < UW) cell[k] = make_uint4(c[0], c[1], c[2], c[3]);
@@ -868,6 +880,13 @@ __device__ __forceinline__ void pack3_fused(const int8_t *__restrict__ gt, int R
         pslot = slot;
         pround8 = round8;
         if (++slot == PACK_FUSE_NB) { slot = 0; round8 += 8; }
+    };
+    // (two iterations per trip, so that no instruction moves one row set into the other; an odd count leaves in the middle)
+#pragma unroll 1
+    for (int it = 0; it < nit; it += 2) {
+        iteration(it, da, db);
+        if (it + 1 == nit) break;
+        iteration(it + 1, db, da);
     }
     wait_ge(&ready[pslot], pround8 + 8);
 #pragma unroll

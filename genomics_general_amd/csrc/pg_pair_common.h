@@ -36,6 +36,34 @@ PG_HD bool pg_deal_window(unsigned block, int per_win, int n_win, int &win, int 
 // the grid that pg_deal_window expects
 inline int64_t pg_deal_blocks(int n_win, int64_t per_win) { return (int64_t)((n_win + 7) / 8) * per_win * 8; }
 
+// The rows of every eighth word (32 sites) of a window part, as the waves of k_pack3's fused form read them: each word behind a
+// buffer descriptor of its own, base = the word's first row, records = the bytes of its rows inside the part.  A part may be longer
+// than 32-bit offsets reach, so the base stays in 64 bits and only offsets inside a word go through the descriptor's range check.
+// From one word of a wave to its next the base moves by 8 * 32 rows (an add with carry) and the rows left shrink by 256; a word
+// past the part, or past the window's end inside the part's last word, has its rows clipped to 0 .. 32, and zero records read as zero
+// whatever the base.  Plain C++, so that a CPU program can walk it (tests/word_walk_main.cpp).
+struct PgWordWalk {
+    uint64_t base;                           // address of the word's first row
+    int left;                                // rows from there to the end of the part (or of the window); may be negative
+
+    // word w0 of the window [lo, hi) of rows of RS bytes at `rows`; the part ends before word w_end
+    PG_HD void start(uint64_t rows, int RS, int64_t lo, int64_t hi, int w_end, int w0) {
+        const int64_t end = hi < lo + 32ll * w_end ? hi : lo + 32ll * w_end, row = lo + 32ll * w0;
+        base = rows + (uint64_t)row * (uint64_t)RS;
+        left = (int)(end - row);             // a part stays below 2^23 sites (pg_exact_parts) and w0 within eight words of it
+    }
+    // (the product between the two clips keeps them a scalar min and a scalar max: clipped back to back they become one
+    // three-operand median, a vector instruction, and a descriptor in vector registers is loaded through in a loop over its values)
+    PG_HD int records(int RS) const {
+        const int n = (left > 32 ? 32 : left) * RS;
+        return n < 0 ? 0 : n;
+    }
+    PG_HD void advance(int RS) {
+        base += (uint64_t)(8 * 32) * (uint64_t)RS;
+        left -= 8 * 32;
+    }
+};
+
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 
