@@ -157,6 +157,24 @@ SIGNATURES = {
     "pg_eig_dev_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "pg_eig_dev_text": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
     "pg_eig_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_s2g_strip": (C.c_int64, [C.c_char_p, C.c_int64, C.c_void_p, C.c_int]),
+    "pg_s2g_text": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                C.c_int]),
+    "pg_s2g_dev_begin": (C.c_int, [_P, C.c_int64]),
+    "pg_s2g_dev_submit": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int64]),
+    "pg_s2g_dev_submit_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_char_p, C.c_int64, C.c_int64]),
+    "pg_s2g_dev_parse": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int]),
+    "pg_s2g_dev_collect": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_s2g_dev_heads": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
+    "pg_s2g_dev_text": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "pg_s2g_dev_put": (C.c_int, [_P, C.c_int64, C.c_void_p, C.c_int64]),
+    "pg_s2g_dev_get": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_void_p]),
+    "pg_s2g_dev_plan": (C.c_int, [_P, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_int, C.POINTER(C.c_int)]),
+    "pg_s2g_dev_emit": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64)]),
+    "pg_s2g_dev_rows": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64]),
+    "pg_s2g_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pg_ped_text": (C.c_int, [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int64, C.c_int, C.c_void_p]),
     "pg_ped_free": (None, [C.c_void_p]),
     "pg_ped_dev_config": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

@@ -2082,3 +2082,14 @@ def genotoplink_main(argv=None):
     transposed into PED rows by k_ped_lines / k_ped_tile, the .map rows written by k_ped_map"""
     from . import genoplink
     return genoplink.main(argv)
+
+
+# ==========================================================================================================
+# seqToGeno.py  (fasta / phylip alignments as .geno sites; genomics_general_amd/seqgeno.py)
+# ==========================================================================================================
+@guarded_main
+def seqtogeno_main(argv=None):
+    """Drop-in for the reference's seqToGeno.py (seqToGeno.py:38-98): the sequences are gathered into a residue store by k_s2g_lines /
+    k_s2g_gather and transposed back into site lines by k_s2g_tile"""
+    from . import seqgeno
+    return seqgeno.main(argv)

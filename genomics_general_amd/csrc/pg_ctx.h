@@ -289,6 +289,24 @@ struct pg_ctx {
         } s[2];
         int64_t blocks = 0, host_blocks = 0;
     } ped;
+    // sequences written as .geno sites on the device (pg_s2g_dev.hip): the residue store, per text slot of the tokenizer the fasta lines'
+    // records and places, the output's description (row template, its share per tile of haplotypes, the segments' names and store
+    // offsets) and the rows of the range in hand
+    struct S2gDev {
+        bool configured = false, planned = false;
+        DevBuf<uint8_t> store, names, out, jobs;
+        DevBuf<int32_t> tmpl, tstart;
+        DevBuf<int64_t> name_off, hap_off, est;
+        HostPin<int64_t> h_est;
+        std::vector<int64_t> h_name_off, h_seg_sites;
+        int tmpl_len = 0, n_haps = 0, tile_seqs = 0, n_tiles = 0;
+        int64_t n_segs = 0, store_len = 0, out_len = 0;
+        struct Slot : LineSlot {
+            DevBuf<uint32_t> cnt, head;                    // per line: its residues, 1 for a head line
+            DevBuf<int64_t> roff, hrow, hrec;              // the lines' places, the head lines' ranks and records
+        } s[2];
+        int64_t blocks = 0, host_blocks = 0, out_ranges = 0;
+    } s2g;
     int64_t tok_nl_fallbacks = 0;                         // deflated blocks whose line feeds were found by passes over the text after all
     HostPin<uint8_t> tok_pin;                              // two 4 MiB page-locked buffers per staging thread
     hipStream_t tok_st[PG_TOK_WORKERS] = {};               // one copy stream per staging thread

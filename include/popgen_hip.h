@@ -997,6 +997,50 @@ int pg_merge_dev_timing(pg_ctx *ctx, int on);
 int pg_merge_dev_stats(pg_ctx *ctx, int64_t *rounds_out, double *keys_ms_out, double *match_ms_out, double *emit_ms_out);
 int pg_merge_dev_end(pg_ctx *ctx);
 
+/* ---- sequences written as `.geno` sites (the seqToGeno.py drop-in, genomics_general_amd/seqgeno.py) --------------------------------
+ * Replaces seqToGeno.py:38-98 -- parseFasta (genomics.py:2256-2261), haploToPhased (412-446) and the per-site joins -- with two
+ * stages that meet in a residue store: the sequences' characters side by side, feeds and blanks gone.  The per-byte and per-line
+ * rules are csrc/pg_s2g_core.h.  A line of the output is name '\t' str(x + 1) '\t' and the bytes of a row template: per byte
+ * -1 - literal ('\t', '|', '\n'), or the index h of a haplotype, whose residue at site x stands at store[hap_off[h] + x].
+ * Host route: pg_s2g_strip copies text[0 .. len) without its line feeds and blanks to dst (room for len bytes) and returns the bytes
+ * written; pg_s2g_text writes the lines x0 .. x1 - 1 of a segment to out and returns out_len, which must be what the closed form
+ * gives (pgs_line_start), else -1. */
+int64_t pg_s2g_strip(const char *text, int64_t len, uint8_t *dst, int n_threads);
+int64_t pg_s2g_text(const uint8_t *store, const char *name, int32_t name_len, const int64_t *hap_off, const int32_t *tmpl, int32_t tmpl_len,
+                    int64_t x0, int64_t x1, uint8_t *out, int64_t out_len, int n_threads);
+/* Device route (csrc/pg_s2g_dev.hip); the store lives on the device:
+ *   pg_s2g_dev_begin          the store, with room for store_hint residues to begin with (it grows)
+ *   pg_s2g_dev_submit / _submit_bgzf   a fasta block of whole lines into text slot `slot` (csrc/pg_line_slot.h), as pg_ped_dev_*
+ *   pg_s2g_dev_parse          k_s2g_lines marks head lines, flags irregular bytes and counts residues, two scans rank the head lines
+ *                             and place the lines, k_s2g_heads writes the head lines' records, k_s2g_gather copies the sequence
+ *                             lines to store[base ..); open: a record is open where the block begins
+ *   pg_s2g_dev_collect        waits.  *host_line_out < 0: *n_res_out residues stand behind base, *n_heads_out head lines were seen
+ *                             (pg_s2g_dev_heads: three words each -- where the line begins in the text, its bytes, the block's
+ *                             residues in front of it); else the block goes to pg_s2g_strip and back by pg_s2g_dev_put
+ *   pg_s2g_dev_text           bytes of the collected block's text; pg_s2g_dev_put / _get: residues to / from the store
+ *   pg_s2g_dev_plan           the output's description: the template (every haplotype once, in rising order), n_segs segments with
+ *                             their names, sites and, per segment and haplotype, the store offset; tile_seqs: haplotypes per tile of
+ *                             k_s2g_tile (0: as many as the LDS holds)
+ *   pg_s2g_dev_emit           a range of the output: piece k the lines x0[k] .. x1[k] - 1 of segment seg[k]; k_s2g_tile writes
+ *                             them, bgzf != 0: k_deflate makes BGZF members of them (pg_s2g_dev_rows: which = 0 rows, 1 members) */
+int pg_s2g_dev_begin(pg_ctx *ctx, int64_t store_hint);
+int pg_s2g_dev_submit(pg_ctx *ctx, int slot, const char *text, int64_t len);
+int pg_s2g_dev_submit_bgzf(pg_ctx *ctx, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                           const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                           int64_t text_len);
+int pg_s2g_dev_parse(pg_ctx *ctx, int slot, int64_t base, int open);
+int pg_s2g_dev_collect(pg_ctx *ctx, int slot, int64_t *n_res_out, int64_t *n_heads_out, int64_t *host_line_out, int64_t *n_lines_out);
+int pg_s2g_dev_heads(pg_ctx *ctx, int slot, int64_t *dst, int64_t n_heads);
+int pg_s2g_dev_text(pg_ctx *ctx, int slot, int64_t off, int64_t len, uint8_t *dst);
+int pg_s2g_dev_put(pg_ctx *ctx, int64_t off, const uint8_t *src, int64_t len);
+int pg_s2g_dev_get(pg_ctx *ctx, int64_t off, int64_t len, uint8_t *dst);
+int pg_s2g_dev_plan(pg_ctx *ctx, const int32_t *tmpl, int32_t tmpl_len, int32_t n_haps, const char *names, const int64_t *name_off,
+                    int64_t n_segs, const int64_t *seg_sites, const int64_t *hap_off, int64_t store_len, int tile_seqs, int *tile_seqs_out);
+int pg_s2g_dev_emit(pg_ctx *ctx, const int32_t *seg, const int64_t *x0, const int64_t *x1, int64_t n_pieces, int64_t out_len, int bgzf,
+                    int64_t *bgzf_len_out);
+int pg_s2g_dev_rows(pg_ctx *ctx, int which, uint8_t *dst, int64_t len);
+int pg_s2g_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out, int64_t *out_ranges_out);
+
 #ifdef __cplusplus
 }
 #endif
