@@ -128,7 +128,7 @@ class _Plan:
         self.contig_flags = np.ascontiguousarray(contig_flags if len(contig_flags) else [0], dtype=np.uint8)
 
     def args(self):
-        vp = lambda a: C.c_void_p(a.ctypes.data)                           # noqa: E731
+        vp = devroute.vp
         return (C.c_void_p(C.addressof(self.cfg)), vp(self.sel_col), vp(self.sel_ploidy), vp(self.sel_popmask), self.contigs, len(self.contigs),
                 vp(self.contig_flags))
 
@@ -152,33 +152,25 @@ class _Device(devroute.SlotDevice):
     BGZF members (k_deflate)"""
 
     def __init__(self, plan, device, gz_rows=False):
-        super().__init__(device)
+        super().__init__(device, "filter")
         taken = C.c_int()
         _lib.check(self.L.pg_filter_dev_config(self.eng._h, *plan.args(), C.byref(taken)))
         self.taken = bool(taken.value)
         _lib.check(self.L.pg_filter_dev_set_output(self.eng._h, int(bool(gz_rows))))
 
-    def submit(self, block, first_line):
-        return self._submit(block, self.L.pg_filter_dev_submit, self.L.pg_filter_dev_submit_bgzf, self.L.pg_filter_dev_parse, first_line)
+    # submit(block, first_line): devroute.SlotDevice's
 
     def collect(self, ticket):
         """(rows, members, text, lines): the rows as text or as BGZF members; rows and members None: the block is the host's, `text` its
         text"""
-        s, keep = ticket
+        s = ticket[0]
         rl, nr, hl, bl, nl = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self.L.pg_filter_dev_collect(self.eng._h, s, C.byref(rl), C.byref(nr), C.byref(hl), C.byref(bl), C.byref(nl)))
         if hl.value >= 0:
-            if isinstance(keep, bytes):
-                return None, None, keep, nl.value
-            return None, None, devroute.fetch(self.L.pg_filter_dev_text, self.eng._h, len(keep[0]), s).tobytes(), nl.value
+            return None, None, self.host_text(ticket), nl.value
         if bl.value:
             return None, (devroute.fetch(self.L.pg_filter_dev_rows_bgzf, self.eng._h, bl.value, s).tobytes(), nr.value), None, nl.value
         return devroute.fetch(self.L.pg_filter_dev_rows, self.eng._h, rl.value, s).tobytes(), None, None, nl.value
-
-    def stats(self):
-        b, h = C.c_int64(), C.c_int64()
-        _lib.check(self.L.pg_filter_dev_stats(self.eng._h, C.byref(b), C.byref(h)))
-        return b.value, h.value
 
 
 def filter_main(argv=None):
@@ -275,8 +267,7 @@ def filter_main(argv=None):
     else:
         ploidyDict = dict(zip(samples, [None] * len(samples)))
 
-    out = genoio.BgzfWriter(args.outfile) if args.outfile and args.outfile.endswith(".gz") else (
-        open(args.outfile, "wb") if args.outfile else sys.stdout.buffer)
+    out = devroute.open_rows(args.outfile)
     ok = False
     try:
         if args.outputGenoFormat != "bases":
@@ -290,13 +281,7 @@ def filter_main(argv=None):
         ok = rc == 0
         return rc
     finally:
-        if out is not sys.stdout.buffer:
-            if ok or not hasattr(out, "abort"):
-                out.close()
-            else:
-                out.abort()
-        else:
-            out.flush()
+        devroute.close_rows(out, ok)
 
 
 def _run(args, reader, out, headers, samples, popNames, popDict, ploidyDict, include, exclude, HWE_P, minPopCallsDict, minPopAllelesDict,
@@ -399,74 +384,41 @@ def _run(args, reader, out, headers, samples, popNames, popDict, ploidyDict, inc
     # inflate them) or PG_BGZF_DEVICE=0
     spans = (dev is not None and not thin and isinstance(getattr(reader, "f", None), genoio.BgzfFile)
              and os.environ.get("PG_BGZF_DEVICE", "1") != "0")
-    pending = None                          # the ticket of the block on the device
-    first = 0
-    carry = b""
-    host_rest = False
-    blocks = devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-filter-read")
-    for blk in blocks:
-        eof = not len(blk)
-        if isinstance(blk, genoio.BgzfSpan):
-            if eof:
-                break
-            info["blocks"] += 1
-            info["blocks_inflated_on_device"] += 1
-            ticket = dev.submit(blk, first)
-            if pending is not None:
-                rc = finish(dev.collect(pending))
-                if rc:
-                    return rc
-            pending = ticket
-            continue
-        data = carry + blk if carry else blk
-        carry = b""
-        if not data:
-            break
-        if cfg.universal_newlines and b"\r" in data:    # universal newlines: the rest is the host's, in one piece (its pods counted there)
-            data += b"".join(blocks)
-            host_rest = eof = True
-        elif thin and not eof:              # whole pods per block: the lines after the last pod boundary wait for the next block
-            nl = np.flatnonzero(np.frombuffer(data, dtype=np.uint8) == 10)
-            take = ((first + len(nl)) // pod) * pod - first
-            if take <= 0:
-                carry = data
-                continue
-            cut = int(nl[take - 1]) + 1
-            data, carry = data[:cut], data[cut:]
-        n_lines = data.count(b"\n") + (0 if data.endswith(b"\n") else 1)
-        info["blocks"] += 1
-        if dev is not None and not host_rest:
-            ticket = dev.submit(data, first)
-            if pending is not None:
-                rc = finish(dev.collect(pending))
-                if rc:
-                    return rc
-            pending = ticket
-        else:
-            if pending is not None:
-                rc = finish(dev.collect(pending))
-                pending = None
-                if rc:
-                    return rc
-            rc = finish((None, None, data, n_lines))
-            if rc:
-                return rc
-        first += n_lines
+    first = [0]                             # data lines of the text handed on so far: the line index the device is given
+
+    def submit(block):
+        ticket = dev.submit(block, first[0])
+        if not devroute.is_span(block):
+            first[0] += devroute.count_lines(block)
+        return ticket
+
+    def host(text, n_lines):
+        first[0] += n_lines
+        return finish((None, None, text, n_lines))
+
+    def whole_pods(data, lines_before, eof):
+        """--thinDist: whole pods per block, the lines after the last pod boundary wait for the next block (a rest that is the
+        host's in one piece has its pods counted there)"""
         if eof:
-            break
-    if pending is not None:
-        rc = finish(dev.collect(pending))
-        if rc:
-            return rc
+            return data, b""
+        nl = np.flatnonzero(np.frombuffer(data, dtype=np.uint8) == 10)
+        take = ((lines_before + len(nl)) // pod) * pod - lines_before
+        if take <= 0:
+            return b"", data
+        at = int(nl[take - 1]) + 1
+        return data[:at], data[at:]
+
+    blocks = devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-filter-read")
+    rc = devroute.run_blocks(blocks, dev, info, finish, host, submit=submit, universal=bool(cfg.universal_newlines),
+                             cut=whole_pods if thin else None)
+    if rc:
+        return rc
     if dev is not None:
         info["device_blocks"], info["device_host_blocks"] = dev.stats()
         dev.close()
     info["total_s"] = time.perf_counter() - t0
     info["filter_s"] = time.perf_counter() - t_ctx
-    last_info.clear()
-    last_info.update(info)
-    if os.environ.get("PG_TIMING"):
-        sys.stderr.write("PG_TIMING filter %s\n" % " ".join("%s=%s" % kv for kv in sorted(info.items())))
+    devroute.report(last_info, info, "filter")
     return 0
 
 

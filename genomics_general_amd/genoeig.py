@@ -45,12 +45,8 @@ ENGINE_EPILOG = ("MI355X engine: blocks of the regular spelling (single tabs, th
 last_info = {}
 
 
-class Usage(SystemExit):
-    """a command line or an input the drop-in does not take: one line on stderr, exit status 2"""
-
-    def __init__(self, msg):
-        sys.stderr.write("genoToEigenstrat.py: " + msg + "\n")
-        super().__init__(2)
+class Usage(devroute.Usage):
+    prog = "genoToEigenstrat.py"
 
 
 class EigCfg(C.Structure):
@@ -77,8 +73,7 @@ def make_parser():
     return ap
 
 
-def _vp(a):
-    return C.c_void_p(a.ctypes.data)
+_vp = devroute.vp
 
 
 class _Plan:
@@ -124,7 +119,7 @@ def host_eig(plan, text, n_threads=0):
     moves on"""
     L = _lib.lib()
     buf = text if isinstance(text, bytes) else bytes(text)
-    n_threads = n_threads or min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 64)
+    n_threads = devroute.host_threads(n_threads)
     n_lines = buf.count(b"\n") + buf.count(b"\r") + 1
     gcap, scap = n_lines * (plan.cfg.n_sel + 1) + 64, n_lines * (40 + plan.max_label) + 64
     scaf = C.create_string_buffer(max(len(buf), len(plan.scaf), 1))
@@ -148,7 +143,7 @@ class _Device(devroute.SlotDevice):
     """the device route (devroute.SlotDevice): one block converted while the next is submitted"""
 
     def __init__(self, plan, device):
-        super().__init__(device)
+        super().__init__(device, "eig")
         self.n_sel = plan.cfg.n_sel
         taken = C.c_int()
         _lib.check(self.L.pg_eig_dev_config(self.eng._h, C.c_void_p(C.addressof(plan.cfg)), _vp(plan.sel_col), plan.names, _vp(plan.name_off),
@@ -158,26 +153,18 @@ class _Device(devroute.SlotDevice):
     def submit(self, block, first_site):
         """the ticket, the site index the block was given and the number of its lines"""
         n_lines = C.c_int64()
-        parse = lambda h, s: self.L.pg_eig_dev_parse(h, s, first_site, C.byref(n_lines))        # noqa: E731
-        ticket = self._submit(block, self.L.pg_eig_dev_submit, self.L.pg_eig_dev_submit_bgzf, parse)
+        ticket = super().submit(block, parse_tail=(first_site, C.byref(n_lines)))
         return ticket, first_site, n_lines.value
 
     def collect(self, ticket, as_text=False):
         """(.geno rows, .snp rows, text, lines): rows None: the block is the host's (or, as_text, the caller's wish), `text` its text"""
-        s, keep = ticket
+        s = ticket[0]
         sl, nr, hl, nl = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self.L.pg_eig_dev_collect(self.eng._h, s, C.byref(sl), C.byref(nr), C.byref(hl), C.byref(nl)))
         if hl.value >= 0 or as_text:
-            if isinstance(keep, bytes):
-                return None, None, keep, nl.value
-            return None, None, devroute.fetch(self.L.pg_eig_dev_text, self.eng._h, len(keep[0]), s).tobytes(), nl.value
+            return None, None, self.host_text(ticket), nl.value
         geno = devroute.fetch(self.L.pg_eig_dev_rows, self.eng._h, nr.value * (self.n_sel + 1), s, 0).tobytes()
         return geno, devroute.fetch(self.L.pg_eig_dev_rows, self.eng._h, sl.value, s, 1).tobytes(), None, nl.value
-
-    def stats(self):
-        b, h = C.c_int64(), C.c_int64()
-        _lib.check(self.L.pg_eig_dev_stats(self.eng._h, C.byref(b), C.byref(h)))
-        return b.value, h.value
 
 
 def read_chrom_file(path):
@@ -212,16 +199,7 @@ def genoeig_main(argv=None):
     chrom = read_chrom_file(args.chromFile) if args.chromFile else {}
 
     reader = genoio.BlockReader(args.genoFile)
-    head = reader.read_header()
-    carry = b""
-    if universal and b"\r" in head:                        # the header ends where the text-mode file ends it
-        head, _, carry = head.partition(b"\r")
-        carry = carry[1:] if carry.startswith(b"\n") else carry
-    if not head:
-        raise Usage("%s is empty: no header line" % shown)
-    if not head.isascii():
-        raise Usage("%s line 1: %s" % (shown, ERRORS[7]))
-    headers = head.decode("ascii").split()
+    headers, carry = devroute.geno_header(reader, universal, shown, Usage)
     all_names = headers[2:]
     if not all_names:
         raise Usage("%s line 1: the header names no sample (the reference stops at an assertion at the first site)" % shown)
@@ -320,66 +298,28 @@ def _run(args, reader, geno_out, snp_out, plan, carry, shown, world, t0):
         done[0] += n_lines
         return None
 
-    def finish_pending(pending):
-        ticket, first, _ = pending
+    flying = [None]                         # the block on the device: (ticket, the site index it was given, its lines)
+
+    def submit(blk):
+        flying[0] = dev.submit(blk, plan.state.sites + (flying[0][2] if flying[0] is not None else 0))
+        return flying[0]
+
+    def collect(block):
+        ticket, first, _ = block
+        if block is flying[0]:
+            flying[0] = None
         stale = first != plan.state.sites   # the block before held '#' lines: the index this one was given is not its own
         if stale:
             info["blocks_redone_on_host"] += 1
-        return finish(dev.collect(ticket, as_text=stale))
+        return dev.collect(ticket, as_text=stale)
 
     spans = (dev is not None and not carry and isinstance(getattr(reader, "f", None), genoio.BgzfFile)
              and os.environ.get("PG_BGZF_DEVICE", "1") != "0")
-    pending = None                          # the block on the device
-    host_rest = False
     blocks = devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-eig-read")
-
-    def submit(blk):
-        nonlocal pending
-        first = plan.state.sites + (pending[2] if pending is not None else 0)
-        nxt = dev.submit(blk, first)
-        rc = finish_pending(pending) if pending is not None else None
-        pending = nxt
+    rc = devroute.run_blocks(blocks, dev, info, finish, lambda text, n_lines: finish((None, None, text, n_lines)), submit=submit,
+                             collect=collect, universal=bool(cfg.universal_newlines), carry=carry)
+    if rc:
         return rc
-
-    for blk in blocks:
-        eof = not len(blk)
-        if isinstance(blk, genoio.BgzfSpan):
-            if eof:
-                break
-            info["blocks"] += 1
-            info["blocks_inflated_on_device"] += 1
-            rc = submit(blk)
-            if rc:
-                return rc
-            continue
-        data = carry + blk if carry else blk
-        carry = b""
-        if not data:
-            break
-        if cfg.universal_newlines and b"\r" in data:    # universal newlines: the rest is the host's, in one piece
-            data += b"".join(blocks)
-            host_rest = eof = True
-        n_lines = data.count(b"\n") + (0 if data.endswith(b"\n") else 1)
-        info["blocks"] += 1
-        if dev is not None and not host_rest:
-            rc = submit(data)
-            if rc:
-                return rc
-        else:
-            if pending is not None:
-                rc = finish_pending(pending)
-                pending = None
-                if rc:
-                    return rc
-            rc = finish((None, None, data, n_lines))
-            if rc:
-                return rc
-        if eof:
-            break
-    if pending is not None:
-        rc = finish_pending(pending)
-        if rc:
-            return rc
     if dev is not None:
         info["device_blocks"], info["device_host_blocks"] = dev.stats()
         dev.close()
@@ -387,10 +327,7 @@ def _run(args, reader, geno_out, snp_out, plan, carry, shown, world, t0):
     info["sites"] = plan.state.sites
     info["total_s"] = time.perf_counter() - t0
     info["eig_s"] = time.perf_counter() - t_ctx
-    last_info.clear()
-    last_info.update(info)
-    if os.environ.get("PG_TIMING"):
-        sys.stderr.write("PG_TIMING eig %s\n" % " ".join("%s=%s" % kv for kv in sorted(info.items())))
+    devroute.report(last_info, info, "eig")
     return 0
 
 

@@ -46,20 +46,12 @@ ENGINE_EPILOG = ("MI355X engine: blocks of the regular spelling (single tabs, th
 last_info = {}
 
 
-class Usage(SystemExit):
-    """a command line or a header the drop-in does not take: one line on stderr, exit status 2"""
-
-    def __init__(self, msg):
-        sys.stderr.write("genoToPlink.py: " + msg + "\n")
-        super().__init__(2)
+class Usage(devroute.Usage):
+    prog = "genoToPlink.py"
 
 
-class Stop(SystemExit):
-    """a line the reference dies on: one line on stderr, exit status 1"""
-
-    def __init__(self, msg):
-        sys.stderr.write("genoToPlink.py: " + msg + "\n")
-        super().__init__(1)
+class Stop(devroute.Stop):
+    prog = "genoToPlink.py"
 
 
 class PedCfg(C.Structure):
@@ -85,8 +77,7 @@ def make_parser():
     return ap
 
 
-def _vp(a):
-    return C.c_void_p(a.ctypes.data)
+_vp = devroute.vp
 
 
 def alleles(fmt, m):
@@ -119,7 +110,7 @@ def host_ped(plan, text, n_threads=0):
     """pg_ped_text on a block of lines ended by \\n: (block, error code, line index in the block)"""
     L = _lib.lib()
     buf = text if isinstance(text, bytes) else bytes(text)
-    n_threads = n_threads or min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 64)
+    n_threads = devroute.host_threads(n_threads)
     blk = PedBlock()
     _lib.check(L.pg_ped_text(C.c_void_p(C.addressof(plan.cfg)), _vp(plan.sel_col), buf, len(buf), n_threads, C.byref(blk)))
     try:
@@ -147,15 +138,7 @@ def matrix_block(sel_len, w, woff, pitch, data, map_rows, run, start, text_at):
     """the block of a device matrix: sample q's w[q] bytes a site begin at woff[q] x pitch; run / start: per site 1 where it opens a
     run, where its line begins in the text; text_at(a, k): the text's bytes [a, a + k)"""
     starts = np.flatnonzero(run)
-    names = []
-    for a in start[starts]:
-        a, k = int(a), 64
-        while True:
-            piece = text_at(a, k)
-            if b"\t" in piece:
-                break
-            k *= 4
-        names.append(piece[:piece.index(b"\t")])
+    names = [devroute.field_at(text_at, int(a)) for a in start[starts]]
     nr, nq, n = len(starts), len(w), len(run)
     run_n = np.diff(np.concatenate([starts, [n]])).astype(np.int64)
     mins = np.broadcast_to(np.asarray(sel_len, dtype=np.int64), (nr, nq))
@@ -168,7 +151,7 @@ class _Device(devroute.SlotDevice):
     """the device route (devroute.SlotDevice): one block transposed while the next is submitted"""
 
     def __init__(self, plan, device, sel_len, tile_seqs=0):
-        super().__init__(device)
+        super().__init__(device, "ped")
         self.plan = plan
         self.sel_len = np.ascontiguousarray(sel_len, dtype=np.int32)
         taken = C.c_int()
@@ -178,13 +161,7 @@ class _Device(devroute.SlotDevice):
         self.w = 2 * alleles(plan.cfg.fmt, self.sel_len)
         self.woff = np.cumsum(self.w) - self.w
 
-    def submit(self, block):
-        return self._submit(block, self.L.pg_ped_dev_submit, self.L.pg_ped_dev_submit_bgzf, self.L.pg_ped_dev_parse)
-
-    def text(self, s, off, n):
-        out = np.empty(max(n, 1), dtype=np.uint8)[:n]
-        _lib.check(self.L.pg_ped_dev_text(self.eng._h, s, off, n, C.c_void_p(out.ctypes.data)))
-        return out.tobytes()
+    # submit(block): devroute.SlotDevice's
 
     def tile_seqs(self):
         t = C.c_int()
@@ -193,13 +170,11 @@ class _Device(devroute.SlotDevice):
 
     def collect(self, ticket):
         """(block, None, lines), or -- the block is the host's -- (None, its text, lines)"""
-        s, keep = ticket
+        s = ticket[0]
         ns, ml, hl, nl, pitch = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self.L.pg_ped_dev_collect(self.eng._h, s, C.byref(ns), C.byref(ml), C.byref(hl), C.byref(nl), C.byref(pitch)))
-        plain = isinstance(keep, bytes)
-        total = len(keep) if plain else len(keep[0])
         if hl.value >= 0:
-            return None, (keep if plain else self.text(s, 0, total)), nl.value
+            return None, self.host_text(ticket), nl.value
         n = ns.value
         # (the matrix up to the last sample's last site, into pageable memory: the rows stay until the input ends, and page-locking
         # them cost more than the faster copy gave back, 0.09 s on 240 MB)
@@ -208,13 +183,7 @@ class _Device(devroute.SlotDevice):
         run, start = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.int64)
         if n:
             _lib.check(self.L.pg_ped_dev_meta(self.eng._h, s, _vp(run), _vp(start)))
-        text_at = (lambda a, k: keep[a:a + k]) if plain else (lambda a, k: self.text(s, a, min(k, total - a)))
-        return matrix_block(self.sel_len, self.w, self.woff, pitch.value, data, map_rows, run, start, text_at), None, nl.value
-
-    def stats(self):
-        b, h = C.c_int64(), C.c_int64()
-        _lib.check(self.L.pg_ped_dev_stats(self.eng._h, C.byref(b), C.byref(h)))
-        return b.value, h.value
+        return matrix_block(self.sel_len, self.w, self.woff, pitch.value, data, map_rows, run, start, self.text_at(ticket)), None, nl.value
 
 
 def first_site_lengths(line, plan):
@@ -274,16 +243,7 @@ def main(argv=None):
     fmt = FMT[args.genoFormat]
 
     reader = genoio.BlockReader(args.genoFile)
-    head = reader.read_header()
-    carry = b""
-    if universal and b"\r" in head:                        # the header ends where the text-mode file ends it
-        head, _, carry = head.partition(b"\r")
-        carry = carry[1:] if carry.startswith(b"\n") else carry
-    if not head:
-        raise Usage("%s is empty: no header line" % shown)
-    if not head.isascii():
-        raise Usage("%s line 1: %s" % (shown, ERRORS[7]))
-    headers = head.decode("ascii").split()
+    headers, carry = devroute.geno_header(reader, universal, shown, Usage)
     all_names = headers[2:]
     if not all_names:
         raise Usage("%s line 1: the header names no sample" % shown)
@@ -329,6 +289,9 @@ def main(argv=None):
         blocks_done.append(blk)
         lines_done[0] += n_lines
 
+    def host(text, n_lines=0):              # (finish counts the lines itself, behind the \r rule)
+        finish((None, text, 0))
+
     # the lines up to the file's first site: their block is the host's, the site's cells set the widths the device is given
     peek = [carry] if carry else []
     first = None
@@ -354,24 +317,10 @@ def main(argv=None):
     try:
         if peek:
             info["blocks"] += 1
-            finish((None, b"".join(peek), 0))
+            host(b"".join(peek))
         spans = (dev is not None and isinstance(getattr(reader, "f", None), genoio.BgzfFile) and os.environ.get("PG_BGZF_DEVICE", "1") != "0")
-        pending = None
-        for blk in devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-ped-read"):
-            if not len(blk):
-                break
-            info["blocks"] += 1
-            if isinstance(blk, genoio.BgzfSpan):
-                info["blocks_inflated_on_device"] += 1
-            if dev is not None:
-                ticket = dev.submit(blk)
-                if pending is not None:
-                    finish(dev.collect(pending))
-                pending = ticket
-            else:
-                finish((None, blk, 0))
-        if pending is not None:
-            finish(dev.collect(pending))
+        blocks = devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-ped-read")
+        devroute.run_blocks(blocks, dev, info, finish, host)
         if dev is not None:
             info["device_blocks"], info["device_host_blocks"] = dev.stats()
         _write(args, prefix, names, fmt, blocks_done, shown, info, t0, t_ctx)
@@ -380,9 +329,7 @@ def main(argv=None):
         if dev is not None:
             dev.close()
     info["close_s"] = time.perf_counter() - t_close
-    last_info.update(info)
-    if os.environ.get("PG_TIMING"):
-        sys.stderr.write("PG_TIMING ped %s\n" % " ".join("%s=%s" % kv for kv in sorted(info.items())))
+    devroute.report(last_info, info, "ped")
     return 0
 
 
@@ -409,5 +356,3 @@ def _write(args, prefix, names, fmt, blocks_done, shown, info, t0, t_ctx):
     info["total_s"] = time.perf_counter() - t0
     info["read_s"] = t_read - t_ctx
     info["write_s"] = time.perf_counter() - t_read
-    last_info.clear()
-    last_info.update(info)

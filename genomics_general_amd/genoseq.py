@@ -14,7 +14,6 @@ import argparse
 import ctypes as C
 import os
 import string
-import sys
 import time
 
 import numpy as np
@@ -39,12 +38,8 @@ ENGINE_EPILOG = ("MI355X engine: blocks of the regular spelling (single tabs, th
 last_info = {}
 
 
-class Usage(SystemExit):
-    """a command line or an input the drop-in does not take: one line on stderr, exit status 2"""
-
-    def __init__(self, msg):
-        sys.stderr.write("genoToSeq.py: " + msg + "\n")
-        super().__init__(2)
+class Usage(devroute.Usage):
+    prog = "genoToSeq.py"
 
 
 class SeqCfg(C.Structure):
@@ -134,7 +129,7 @@ class Plan:
         self.sel_len = np.ascontiguousarray([w for _, _, w in sel], dtype=np.int32)
 
     def args(self):
-        vp = lambda a: C.c_void_p(a.ctypes.data)                    # noqa: E731
+        vp = devroute.vp
         return (C.c_void_p(C.addressof(self.cfg)), vp(self.sel_col), vp(self.sel_off), vp(self.sel_len))
 
 
@@ -180,7 +175,7 @@ class Device(devroute.SlotDevice):
     """the device route (devroute.SlotDevice): one block transposed while the next is submitted"""
 
     def __init__(self, plan, device, tile_seqs=0):
-        super().__init__(device)
+        super().__init__(device, "seq")
         self.configure(plan, tile_seqs)
 
     def configure(self, plan, tile_seqs=0):
@@ -191,47 +186,33 @@ class Device(devroute.SlotDevice):
         _lib.check(self.L.pg_seq_dev_config(self.eng._h, *plan.args(), int(tile_seqs), C.byref(taken)))
         self.taken = bool(taken.value)
 
-    def submit(self, block):
-        return self._submit(block, self.L.pg_seq_dev_submit, self.L.pg_seq_dev_submit_bgzf, self.L.pg_seq_dev_parse)
-
-    def text(self, s, off, n):
-        out = np.empty(max(n, 1), dtype=np.uint8)[:n]               # (pg_seq_dev_text takes the length in front of the destination)
-        _lib.check(self.L.pg_seq_dev_text(self.eng._h, s, off, n, C.c_void_p(out.ctypes.data)))
-        return out.tobytes()
+    # submit(block): devroute.SlotDevice's
 
     def collect(self, ticket, padded=False):
         """(chunk, positions, run starts, run names, None, lines), or -- the block is the host's -- (None, ..., its text, the line the
         device does not take).  padded: the chunk's matrix keeps the device's pitch (the tests look at the pad columns)"""
-        s, keep = ticket
+        s = ticket[0]
         ns, hl, nl, pitch = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self.L.pg_seq_dev_collect(self.eng._h, s, C.byref(ns), C.byref(hl), C.byref(nl), C.byref(pitch)))
-        plain = isinstance(keep, bytes)
         if hl.value >= 0:
-            return None, None, None, None, (keep if plain else self.text(s, 0, len(keep[0]))), hl.value
+            return None, None, None, None, self.host_text(ticket), hl.value
         n, nq = ns.value, self.plan.cfg.n_seq
         width = pitch.value if padded else n
         mat = self.eng.pinned.empty((nq, max(width, 1)), np.uint8)[:, :width]
         if not mat.flags["C_CONTIGUOUS"]:
             mat = np.ascontiguousarray(mat)
         pos, run, start = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.int64)
-        vp = lambda a: C.c_void_p(a.ctypes.data)                                # noqa: E731
+        vp = devroute.vp
         if n:
             _lib.check(self.L.pg_seq_dev_rows(self.eng._h, s, 0, nq, vp(mat), width, width))
             _lib.check(self.L.pg_seq_dev_meta(self.eng._h, s, vp(pos), vp(run), vp(start)))
         starts = np.flatnonzero(run)
-        names = []
-        total = len(keep) if plain else len(keep[0])
-        for a in start[starts]:
-            a, k = int(a), 64
-            while True:
-                piece = keep[a:a + k] if plain else self.text(s, a, min(k, total - a))
-                if b"\t" in piece:
-                    break
-                k *= 4
-            names.append(piece[:piece.index(b"\t")].decode("ascii"))
+        text_at = self.text_at(ticket)
+        names = [devroute.field_at(text_at, int(a)).decode("ascii") for a in start[starts]]
         return Chunk(n, mat=mat, stride=1), pos, starts, names, None, nl.value
 
     def stats(self):
+        """SlotDevice's two counts, and the milliseconds of k_seq_lines and of k_seq_tile"""
         b, h, lm, tm = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
         _lib.check(self.L.pg_seq_dev_stats(self.eng._h, C.byref(b), C.byref(h), C.byref(lm), C.byref(tm)))
         return b.value, h.value, lm.value, tm.value
@@ -305,14 +286,10 @@ def alignment(fmt, names, seqs):
 
 
 def _open_bin(path):
-    if path is None:
-        return sys.stdout.buffer
-    if path.endswith(".gz"):
-        if os.environ.get("PG_OUT_GZIP_MODULE"):
-            import gzip
-            return gzip.open(path, "wb")
-        return genoio.BgzfWriter(path)
-    return open(path, "wb")
+    if path is not None and path.endswith(".gz") and os.environ.get("PG_OUT_GZIP_MODULE"):
+        import gzip
+        return gzip.open(path, "wb")
+    return devroute.open_rows(path)
 
 
 def _check_args(args):
@@ -450,22 +427,8 @@ def main(argv=None):
     ok = False
     try:
         spans = (dev is not None and isinstance(getattr(reader, "f", None), genoio.BgzfFile) and os.environ.get("PG_BGZF_DEVICE", "1") != "0")
-        pending = None
-        for blk in devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-seq-read"):
-            if not len(blk):
-                break
-            info["blocks"] += 1
-            if isinstance(blk, genoio.BgzfSpan):
-                info["blocks_inflated_on_device"] += 1
-            if dev is not None:
-                ticket = dev.submit(blk)
-                if pending is not None:
-                    finish(collect(pending))
-                pending = ticket
-            else:
-                finish((None, None, None, None, blk, 0))
-        if pending is not None:
-            finish(collect(pending))
+        blocks = devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-seq-read")
+        devroute.run_blocks(blocks, dev, info, finish, lambda text, n_lines: finish((None, None, None, None, text, 0)), collect=collect)
         if stream is not None:
             write_windows(True)
         else:                                              # cat: one alignment of everything
@@ -489,16 +452,9 @@ def main(argv=None):
             info["device_blocks"], info["device_host_blocks"], info["k_seq_lines_ms"], info["k_seq_tile_ms"] = dev.stats()
             dev.close()
         if out is not None:
-            if out is sys.stdout.buffer:
-                out.flush()
-            elif ok or not hasattr(out, "abort"):
-                out.close()
-            else:
-                out.abort()
+            devroute.close_rows(out, ok)
         last_info.clear()
         last_info.update(info)
     info["total_s"] = time.perf_counter() - t0
-    last_info.update(info)
-    if os.environ.get("PG_TIMING"):
-        sys.stderr.write("PG_TIMING genoToSeq %s\n" % " ".join("%s=%s" % kv for kv in sorted(info.items())))
+    devroute.report(last_info, info, "genoToSeq")
     return 0

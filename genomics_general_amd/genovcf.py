@@ -44,12 +44,8 @@ ENGINE_EPILOG = ("MI355X engine: blocks of the regular spelling (single tabs, th
 last_info = {}
 
 
-class Usage(SystemExit):
-    """a command line or an input the drop-in does not take: one line on stderr, exit status 2"""
-
-    def __init__(self, msg):
-        sys.stderr.write("genoToVCF.py: " + msg + "\n")
-        super().__init__(2)
+class Usage(devroute.Usage):
+    prog = "genoToVCF.py"
 
 
 class GvcfCfg(C.Structure):
@@ -124,7 +120,7 @@ class _Plan:
                                                C.c_void_p(self.table.ctypes.data), self.mask))
 
     def ref_args(self):
-        vp = lambda a: C.c_void_p(a.ctypes.data)                           # noqa: E731
+        vp = devroute.vp
         return (self.names, vp(self.name_off), vp(self.seq_len), vp(self.seq_off), vp(self.table), self.mask, self.n_seq, vp(self.seq))
 
 
@@ -132,8 +128,7 @@ def host_gvcf(plan, text, n_threads=0):
     """pg_gvcf_text on a block of lines: (rows, error code, line index in the block)"""
     L = _lib.lib()
     buf = text if isinstance(text, bytes) else bytes(text)
-    n_threads = n_threads or min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 64)
-    vp = lambda a: C.c_void_p(a.ctypes.data)                               # noqa: E731
+    n_threads, vp = devroute.host_threads(n_threads), devroute.vp
     cap = 3 * len(buf) + 40 * (buf.count(b"\n") + buf.count(b"\r") + 1) + 64
     while True:
         out = np.empty(cap, dtype=np.uint8)
@@ -150,34 +145,26 @@ class _Device(devroute.SlotDevice):
     BGZF members (k_deflate)"""
 
     def __init__(self, plan, device, gz_rows=False):
-        super().__init__(device)
+        super().__init__(device, "gvcf")
         taken = C.c_int()
         _lib.check(self.L.pg_gvcf_dev_config(self.eng._h, C.c_void_p(C.addressof(plan.cfg)), C.c_void_p(plan.sel_col.ctypes.data),
                                              *plan.ref_args(), plan.seq_bytes, C.byref(taken)))
         self.taken = taken.value
         _lib.check(self.L.pg_gvcf_dev_set_output(self.eng._h, int(bool(gz_rows))))
 
-    def submit(self, block):
-        return self._submit(block, self.L.pg_gvcf_dev_submit, self.L.pg_gvcf_dev_submit_bgzf, self.L.pg_gvcf_dev_parse)
+    # submit(block): devroute.SlotDevice's
 
     def collect(self, ticket):
         """(rows, members, text, lines): the rows as text or as BGZF members; rows and members None: the block is the host's, `text` its
         text"""
-        s, keep = ticket
+        s = ticket[0]
         rl, nr, hl, bl, nl = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         _lib.check(self.L.pg_gvcf_dev_collect(self.eng._h, s, C.byref(rl), C.byref(nr), C.byref(hl), C.byref(bl), C.byref(nl)))
         if hl.value >= 0:
-            if isinstance(keep, bytes):
-                return None, None, keep, nl.value
-            return None, None, devroute.fetch(self.L.pg_gvcf_dev_text, self.eng._h, len(keep[0]), s).tobytes(), nl.value
+            return None, None, self.host_text(ticket), nl.value
         if bl.value:
             return None, (devroute.fetch(self.L.pg_gvcf_dev_rows_bgzf, self.eng._h, bl.value, s).tobytes(), nr.value), None, nl.value
         return devroute.fetch(self.L.pg_gvcf_dev_rows, self.eng._h, rl.value, s).tobytes(), None, None, nl.value
-
-    def stats(self):
-        b, h = C.c_int64(), C.c_int64()
-        _lib.check(self.L.pg_gvcf_dev_stats(self.eng._h, C.byref(b), C.byref(h)))
-        return b.value, h.value
 
 
 def genovcf_main(argv=None):
@@ -209,16 +196,7 @@ def genovcf_main(argv=None):
                     raise Usage("%s.fai line %d: %s" % (args.reference, k + 1, ERRORS[7]))
 
     reader = genoio.BlockReader(args.genoFile)
-    head = reader.read_header()
-    carry = b""
-    if universal and b"\r" in head:                        # the header ends where the text-mode file ends it
-        head, _, carry = head.partition(b"\r")
-        carry = carry[1:] if carry.startswith(b"\n") else carry
-    if not head:
-        raise Usage("%s is empty: no header line" % shown)
-    if not head.isascii():
-        raise Usage("%s line 1: %s" % (shown, ERRORS[7]))
-    headers = head.decode("ascii").split()
+    headers, carry = devroute.geno_header(reader, universal, shown, Usage)
     all_names = headers[2:]
     names_to_use = args.samples.split(",") if args.samples else all_names
     if not all(n.isascii() for n in names_to_use):
@@ -242,8 +220,7 @@ def genovcf_main(argv=None):
     cfg.universal_newlines = int(universal)
     plan = _Plan(cfg, [last_col[n] for n in names_to_use], prev_same, where, seq)
 
-    out = genoio.BgzfWriter(args.outFile) if args.outFile and args.outFile.endswith(".gz") else (
-        open(args.outFile, "wb") if args.outFile else sys.stdout.buffer)
+    out = devroute.open_rows(args.outFile)
     ok = False
     try:
         top = ["##fileformat=VCFv4.2\n"]
@@ -259,13 +236,7 @@ def genovcf_main(argv=None):
         ok = rc == 0
         return rc
     finally:
-        if out is not sys.stdout.buffer:
-            if ok or not hasattr(out, "abort"):
-                out.close()
-            else:
-                out.abort()
-        else:
-            out.flush()
+        devroute.close_rows(out, ok)
 
 
 def _run(args, reader, out, plan, carry, shown, world, t0):
@@ -312,63 +283,17 @@ def _run(args, reader, out, plan, carry, shown, world, t0):
 
     spans = (dev is not None and not carry and isinstance(getattr(reader, "f", None), genoio.BgzfFile)
              and os.environ.get("PG_BGZF_DEVICE", "1") != "0")
-    pending = None                          # the ticket of the block on the device
-    host_rest = False
     blocks = devroute.read_ahead(devroute.blocks(reader, block_bytes, dev.pinned() if spans else None, info), "pg-gvcf-read")
-    for blk in blocks:
-        eof = not len(blk)
-        if isinstance(blk, genoio.BgzfSpan):
-            if eof:
-                break
-            info["blocks"] += 1
-            info["blocks_inflated_on_device"] += 1
-            ticket = dev.submit(blk)
-            if pending is not None:
-                rc = finish(dev.collect(pending))
-                if rc:
-                    return rc
-            pending = ticket
-            continue
-        data = carry + blk if carry else blk
-        carry = b""
-        if not data:
-            break
-        if cfg.universal_newlines and b"\r" in data:    # universal newlines: the rest is the host's, in one piece
-            data += b"".join(blocks)
-            host_rest = eof = True
-        n_lines = data.count(b"\n") + (0 if data.endswith(b"\n") else 1)
-        info["blocks"] += 1
-        if dev is not None and not host_rest:
-            ticket = dev.submit(data)
-            if pending is not None:
-                rc = finish(dev.collect(pending))
-                if rc:
-                    return rc
-            pending = ticket
-        else:
-            if pending is not None:
-                rc = finish(dev.collect(pending))
-                pending = None
-                if rc:
-                    return rc
-            rc = finish((None, None, data, n_lines))
-            if rc:
-                return rc
-        if eof:
-            break
-    if pending is not None:
-        rc = finish(dev.collect(pending))
-        if rc:
-            return rc
+    rc = devroute.run_blocks(blocks, dev, info, finish, lambda text, n_lines: finish((None, None, text, n_lines)),
+                             universal=bool(cfg.universal_newlines), carry=carry)
+    if rc:
+        return rc
     if dev is not None:
         info["device_blocks"], info["device_host_blocks"] = dev.stats()
         dev.close()
     info["total_s"] = time.perf_counter() - t0
     info["gvcf_s"] = time.perf_counter() - t_ctx
-    last_info.clear()
-    last_info.update(info)
-    if os.environ.get("PG_TIMING"):
-        sys.stderr.write("PG_TIMING gvcf %s\n" % " ".join("%s=%s" % kv for kv in sorted(info.items())))
+    devroute.report(last_info, info, "gvcf")
     return 0
 
 

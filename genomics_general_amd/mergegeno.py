@@ -46,12 +46,8 @@ SMALL_INPUT = 4 << 20                # bytes of input files below which the host
 last_info = {}
 
 
-class Usage(SystemExit):
-    """a command line or an input the drop-in does not take: one line on stderr, exit status 2"""
-
-    def __init__(self, msg):
-        sys.stderr.write("mergeGeno.py: " + msg + "\n")
-        super().__init__(2)
+class Usage(devroute.Usage):
+    prog = "mergeGeno.py"
 
 
 class MergeCfg(C.Structure):
@@ -281,7 +277,7 @@ def main(argv=None):
                    sum(1 << x for x in set(output_idx)), len(sep), len(missing), fai.n)
 
     gz_out = bool(args.outputFile and args.outputFile.endswith(".gz"))
-    out = genoio.BgzfWriter(args.outputFile) if gz_out else (open(args.outputFile, "wb") if args.outputFile else sys.stdout.buffer)
+    out = devroute.open_rows(args.outputFile)
     info = dict(rounds=0, rounds_on_device=0, rounds_on_host=0, blocks=0, blocks_inflated_on_device=0, lines_written=0, stopped_files=0,
                 rounds_deflated_on_device=0, text_bytes=0, read_s=0.0, device_s=0.0, host_s=0.0, write_s=0.0)
     dev = None
@@ -424,15 +420,9 @@ def main(argv=None):
             dev.close()
         for f in files:
             f.reader.close()
-        if out is sys.stdout.buffer:
-            out.flush()
-        elif ok or not hasattr(out, "abort"):
-            out.close()
-        else:
-            out.abort()
+        devroute.close_rows(out, ok)
         info["total_s"] = time.perf_counter() - t0
         last_info.clear()
         last_info.update(info)
-    if os.environ.get("PG_TIMING"):
-        sys.stderr.write("PG_TIMING mergeGeno %s\n" % " ".join("%s=%s" % kv for kv in sorted(info.items())))
+    devroute.report(last_info, info, "mergeGeno")
     return 0

@@ -39,20 +39,13 @@ MAX_NAME = 4096                                            # PGS_MAX_NAME
 last_info = {}
 
 
-class Usage(SystemExit):
-    """an input or a command line the drop-in does not take: one line on stderr, exit status 2, no output file"""
-
-    def __init__(self, msg):
-        sys.stderr.write("seqToGeno.py: " + msg + "\n")
-        super().__init__(2)
+class Usage(devroute.Usage):
+    """(no output file is left)"""
+    prog = "seqToGeno.py"
 
 
-class Stop(SystemExit):
-    """a line the reference dies on: one line on stderr, exit status 1"""
-
-    def __init__(self, msg):
-        sys.stderr.write("seqToGeno.py: " + msg + "\n")
-        super().__init__(1)
+class Stop(devroute.Stop):
+    prog = "seqToGeno.py"
 
 
 def make_parser():
@@ -77,8 +70,7 @@ def _vp(a):
     return C.c_void_p(a.ctypes.data if a.size else 0)
 
 
-def _threads(n_threads):
-    return n_threads or min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1), 64)
+_threads = devroute.host_threads
 
 
 def digit_sum(x):
@@ -167,28 +159,15 @@ class _Device(devroute.SlotDevice):
     """the device route: the store in device memory, a fasta block's kernels queued while the next block is on its way"""
 
     def __init__(self, device, hint):
-        super().__init__(device)
+        super().__init__(device, "s2g")
         _lib.check(self.L.pg_s2g_dev_begin(self.eng._h, int(hint)))
 
     def submit(self, block):
         """the block into the next slot (its copy, or its members' inflation, queued); the ticket parse and collect take"""
-        s = self.slot
-        self.slot ^= 1
-        if devroute.is_span(block):
-            args, comp = devroute.span_args(block)
-            _lib.check(self.L.pg_s2g_dev_submit_bgzf(self.eng._h, s, *args))
-            return (s, (block, comp))
-        keep = block if isinstance(block, bytes) else bytes(block)
-        _lib.check(self.L.pg_s2g_dev_submit(self.eng._h, s, keep, len(keep)))
-        return (s, keep)
+        return self.load(block)
 
     def parse(self, ticket, base, is_open):
         _lib.check(self.L.pg_s2g_dev_parse(self.eng._h, ticket[0], int(base), int(bool(is_open))))
-
-    def text(self, s, off, n):
-        out = np.empty(max(n, 1), dtype=np.uint8)[:n]
-        _lib.check(self.L.pg_s2g_dev_text(self.eng._h, s, off, n, C.c_void_p(out.ctypes.data)))
-        return out.tobytes()
 
     def collect(self, ticket, rec, n_threads):
         """the block's records into rec; a block the device hands back is stripped here and uploaded to the same place"""
@@ -417,12 +396,6 @@ def host_emit(part, store, pieces, size, n_threads):
     return out
 
 
-def open_output(path):
-    if not path:
-        return sys.stdout.buffer
-    return genoio.BgzfWriter(path) if path.endswith(".gz") else open(path, "wb")
-
-
 def main(argv=None):
     t0 = time.perf_counter()
     args = make_parser().parse_args(argv)
@@ -524,7 +497,7 @@ def main(argv=None):
         t_load = time.perf_counter()
         gz_rows = (dev is not None and bool(args.genoFile and args.genoFile.endswith(".gz"))
                    and os.environ.get("PG_DEFLATE_DEVICE", "1") != "0")
-        out = open_output(args.genoFile)
+        out = devroute.open_rows(args.genoFile)
         out.write(plan.header.encode("ascii"))
         for part in plan.parts:
             if dev is not None:
@@ -542,24 +515,18 @@ def main(argv=None):
                     out.write(memoryview(rows))
         if dev is not None:
             info["device_blocks"], info["device_host_blocks"], info["out_ranges"] = dev.stats()
-        if out is not sys.stdout.buffer:
-            out.close()
-        else:
-            out.flush()
+        devroute.close_rows(out, True)
         out = None
         info["load_s"] = t_load - t_ctx
         info["emit_s"] = time.perf_counter() - t_load
     finally:
-        if out is not None and out is not sys.stdout.buffer:
-            (out.abort if hasattr(out, "abort") else out.close)()
+        if out is not None:
+            devroute.close_rows(out, False)
         if dev is not None:
             dev.close()
         reader.close()
     info["total_s"] = time.perf_counter() - t0
-    last_info.clear()
-    last_info.update(info)
-    if os.environ.get("PG_TIMING"):
-        sys.stderr.write("PG_TIMING s2g %s\n" % " ".join("%s=%s" % kv for kv in sorted(info.items())))
+    devroute.report(last_info, info, "s2g")
     if plan.stop:
         raise Stop(plan.stop)
     return 0
