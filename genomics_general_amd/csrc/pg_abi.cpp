@@ -246,7 +246,7 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
         if (P.done) (void)hipEventDestroy(P.done);
     }
     c->s2g.store.release(); c->s2g.names.release(); c->s2g.out.release(); c->s2g.jobs.release(); c->s2g.tmpl.release(); c->s2g.tstart.release();
-    c->s2g.name_off.release(); c->s2g.hap_off.release(); c->s2g.est.release(); c->s2g.h_est.release();
+    c->s2g.name_off.release(); c->s2g.hap_off.release(); c->s2g.est.status.release(); c->s2g.est.h_status.release();
     for (int k = 0; k < 2; ++k) {
         pg_ctx::S2gDev::Slot &P = c->s2g.s[k];
         P.cnt.release(); P.head.release(); P.roff.release(); P.hrow.release(); P.hrec.release(); P.status.release(); P.h_status.release();

@@ -94,6 +94,22 @@ struct PgLineDev {
     hipEvent_t done = nullptr;           // the block's last copy back
     PgLineSlot L;
 };
+// ... and what the routes themselves count alike: pg_*_dev_config (seqToGeno: _begin) has taken the option set; _set_output: the rows
+// leave the device as BGZF members too; blocks parsed on the device, and those of them that collect handed to the host route
+struct PgLineRoute {
+    bool configured = false, bgzf_rows = false;
+    int64_t blocks = 0, host_blocks = 0;
+};
+
+// text deflated on the device (pg_deflate.hip): token buffers of the persistent waves, the members' streams, sizes and CRC-32s, the
+// assembled BGZF members
+struct PgDeflate {
+    DevBuf<uint32_t> tok, out_len, crc;
+    DevBuf<uint8_t> slots, comp, text;      // text: pg_bgzf_compress_device only
+    DevBuf<int64_t> totals;                 // [0] bytes of text, [1] bytes of the members
+    HostPin<int64_t> h_totals;
+    void release() { tok.release(); out_len.release(); crc.release(); slots.release(); comp.release(); text.release(); totals.release(); h_totals.release(); }
+};
 
 struct pg_ctx {
     using LineSlot = PgLineDev;
@@ -164,19 +180,11 @@ struct pg_ctx {
         int64_t len = 0, n_lines = 0, n_tiles = 0, run_cap = 0;
         int64_t n_members = 0, head_len = 0;   // (a block that arrived deflated)
     } tok[2];
-    // text deflated on the device (pg_deflate.hip): token buffers of the persistent waves, the members' streams, sizes and CRC-32s, the
-    // assembled BGZF members
-    struct Deflate {
-        DevBuf<uint32_t> tok, out_len, crc;
-        DevBuf<uint8_t> slots, comp, text;      // text: pg_bgzf_compress_device only
-        DevBuf<int64_t> totals;                 // [0] bytes of text, [1] bytes of the members
-        HostPin<int64_t> h_totals;
-        void release() { tok.release(); out_len.release(); crc.release(); slots.release(); comp.release(); text.release(); totals.release(); h_totals.release(); }
-    } deflate;
+    using Deflate = PgDeflate;
+    Deflate deflate;
     // VCF lines parsed on the device (pg_vcf_dev.hip): the option set of the run and, per text slot of the tokenizer, the per-line
     // records, the rows' sizes and places, the rows' text
-    struct VcfDev {
-        bool configured = false;
+    struct VcfDev : PgLineRoute {
         PgvConfig cfg;
         int waves_per_block = 4;
         DevBuf<uint8_t> contigs, ploidy, fsel, prevkey;      // prevkey: the PgvKey of the last data line seen (--excludeDuplicates)
@@ -191,14 +199,11 @@ struct pg_ctx {
             hipEvent_t rows_ready = nullptr;
             int64_t out_cap = 0;
         } s[2];
-        bool bgzf_rows = false;                  // pg_vcf_dev_set_output: the rows leave the device as BGZF members
         double kernel_ms = 0;                    // pg_vcf_dev_stats
-        int64_t blocks = 0, host_blocks = 0;
     } vcf;
     // .geno sites filtered on the device (pg_filter_dev.hip): the option set and, per text slot of the tokenizer, the lines' flags,
     // positions, row sizes and places, the rows
-    struct FiltDev {
-        bool configured = false;
+    struct FiltDev : PgLineRoute {
         PgfConfig cfg;
         DevBuf<int32_t> sel_col, sel_ploidy;
         DevBuf<uint32_t> sel_popmask, coff;                 // coff: the contig names' offsets (n_contigs + 1)
@@ -210,13 +215,10 @@ struct pg_ctx {
             Deflate df;                                    // the rows deflated where they lie (pg_filter_dev_set_output)
             int64_t out_cap = 0, first_line = 0;
         } s[2];
-        bool bgzf_rows = false;
-        int64_t blocks = 0, host_blocks = 0;
     } filt;
     // .geno sites written as VCF rows on the device (pg_gvcf_dev.hip): the option set, the fasta (names, their table, the sequences
     // side by side) and, per text slot of the tokenizer, the row sizes and places, the rows
-    struct GvcfDev {
-        bool configured = false;
+    struct GvcfDev : PgLineRoute {
         pg_gvcf_cfg cfg;
         DevBuf<int32_t> sel_col, table;
         DevBuf<uint8_t> names, seq;
@@ -230,14 +232,11 @@ struct pg_ctx {
             Deflate df;                                    // the rows deflated where they lie (pg_gvcf_dev_set_output)
             int64_t out_cap = 0;
         } s[2];
-        bool bgzf_rows = false;
-        int64_t blocks = 0, host_blocks = 0;
     } gvcf;
     // biallelic .geno sites written as EIGENSTRAT rows on the device (pg_eig_dev.hip): the option set, the --chromFile (scaffold names,
     // their table, the labels side by side) and, per text slot of the tokenizer, what the first run leaves per line (the .snp row's
     // size, the site's alleles, the label's entry), the kept lines' ranks and places, the two outputs
-    struct EigDev {
-        bool configured = false;
+    struct EigDev : PgLineRoute {
         pg_eig_cfg cfg;
         DevBuf<int32_t> sel_col, table;
         DevBuf<uint8_t> names, labels;
@@ -250,12 +249,10 @@ struct pg_ctx {
             DevBuf<int64_t> roff, rank;
             int64_t snp_cap = 0, first_site = 0;
         } s[2];
-        int64_t blocks = 0, host_blocks = 0;
     } eig;
     // .geno lines turned into sequences on the device (pg_seq_dev.hip): the option set, the selection tables and, per text slot of the
     // tokenizer, the lines' records, the kept lines' places, the sites' records and the matrix [n_seq][pitch]
-    struct SeqDev {
-        bool configured = false;
+    struct SeqDev : PgLineRoute {
         pg_seq_cfg cfg;
         int tile_seqs = 0;                                 // output sequences per tile of k_seq_tile
         DevBuf<int32_t> sel_col, sel_off, sel_len;
@@ -269,13 +266,11 @@ struct pg_ctx {
         } s[2];
         bool timing = false;
         double lines_ms = 0, tile_ms = 0;
-        int64_t blocks = 0, host_blocks = 0;
     } seq;
     // .geno sites written as PED rows and MAP lines on the device (pg_ped_dev.hip): the option set, per sample its column, the length
     // its cells must have, the bytes a site takes in its row (2 a_q) and their sum over the samples before; per text slot of the
     // tokenizer the lines' records, the kept lines' places, the .map rows and the matrix (sample q's row at woff[q] x pitch)
-    struct PedDev {
-        bool configured = false;
+    struct PedDev : PgLineRoute {
         pg_ped_cfg cfg;
         int tile_seqs = 0, wmax = 0;                       // samples per tile of k_ped_tile; the widest sample's bytes a site
         int64_t wsum = 0;                                  // bytes a site takes over all samples
@@ -287,17 +282,16 @@ struct pg_ctx {
             DevBuf<int64_t> row, roff, rstart, line_of;
             int64_t pitch = 0, map_cap = 0;
         } s[2];
-        int64_t blocks = 0, host_blocks = 0;
     } ped;
     // sequences written as .geno sites on the device (pg_s2g_dev.hip): the residue store, per text slot of the tokenizer the fasta lines'
     // records and places, the output's description (row template, its share per tile of haplotypes, the segments' names and store
     // offsets) and the rows of the range in hand
-    struct S2gDev {
-        bool configured = false, planned = false;
+    struct S2gDev : PgLineRoute {
+        bool planned = false;
         DevBuf<uint8_t> store, names, out, jobs;
         DevBuf<int32_t> tmpl, tstart;
-        DevBuf<int64_t> name_off, hap_off, est;
-        HostPin<int64_t> h_est;
+        DevBuf<int64_t> name_off, hap_off;
+        PgLineDev est;                                     // pg_s2g_dev_emit: the status words k_deflate reads and answers through
         std::vector<int64_t> h_name_off, h_seg_sites;
         int tmpl_len = 0, n_haps = 0, tile_seqs = 0, n_tiles = 0;
         int64_t n_segs = 0, store_len = 0, out_len = 0;
@@ -305,7 +299,7 @@ struct pg_ctx {
             DevBuf<uint32_t> cnt, head;                    // per line: its residues, 1 for a head line
             DevBuf<int64_t> roff, hrow, hrec;              // the lines' places, the head lines' ranks and records
         } s[2];
-        int64_t blocks = 0, host_blocks = 0, out_ranges = 0;
+        int64_t out_ranges = 0;
     } s2g;
     int64_t tok_nl_fallbacks = 0;                         // deflated blocks whose line feeds were found by passes over the text after all
     HostPin<uint8_t> tok_pin;                              // two 4 MiB page-locked buffers per staging thread

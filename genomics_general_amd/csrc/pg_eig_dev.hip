@@ -7,7 +7,7 @@
 //                   columns classify their cells, the four base counts reduced across the wave; a site of exactly two bases is kept
 //                   (pge_site: its alleles, the counted one); the scaffold's hash summed a lane a byte and looked up in the table over
 //                   the --chromFile's names; the .snp row's size
-//   k_eig_scan      every kept line's rank (its .geno row lies at rank x (n_sel + 1)) and its .snp row's place
+//   scan            every kept line's rank (its .geno row lies at rank x (n_sel + 1)) and its .snp row's place (k_rows_scan, pg_line_slot.hip)
 //   k_eig_lines<1>  a kept line again: lanes strided over the SELECTED columns write their digit; the .snp row: the site's index (the
 //                   block's first plus the line's), the label, the position's text without its leading zeros, the two bases
 // Two outputs per block: the .geno bytes follow from PGL_ST_ROWS, PGL_ST_BYTES counts the .snp bytes.  The text arrives in the
@@ -131,42 +131,7 @@ __global__ __launch_bounds__(64) void k_eig_lines(EigArgs A, PgeConfig cfg) {
         o[at + (uint32_t)lane] = (uint8_t)(lane == 0 || lane == 2 ? '\t' : lane == 1 ? pge_base_char(sb & 3) : lane == 3 ? pge_base_char((sb >> 2) & 3) : '\n');
 }
 
-// one block: the kept lines' ranks, their .snp rows' places (exclusive sums), the rows' total and number
-__global__ __launch_bounds__(1024) void k_eig_scan(const uint32_t *__restrict__ rlen, int64_t n_lines, int64_t *__restrict__ roff,
-                                                    int64_t *__restrict__ rank, long long *__restrict__ status, int64_t out_cap) {
-    __shared__ long long sh[1024], shn[1024];
-    const int64_t per = (n_lines + 1023) / 1024;
-    const int64_t a = std::min<int64_t>(n_lines, (int64_t)threadIdx.x * per), b = std::min<int64_t>(n_lines, a + per);
-    long long mine = 0, rows = 0;
-    for (int64_t k = a; k < b; ++k) {
-        mine += rlen[k];
-        rows += rlen[k] != 0;
-    }
-    sh[threadIdx.x] = mine;
-    shn[threadIdx.x] = rows;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const long long x = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0, y = (int)threadIdx.x >= d ? shn[threadIdx.x - d] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += x;
-        shn[threadIdx.x] += y;
-        __syncthreads();
-    }
-    long long run = sh[threadIdx.x] - mine, r = shn[threadIdx.x] - rows;
-    for (int64_t k = a; k < b; ++k) {
-        roff[k] = run;
-        rank[k] = r;
-        run += rlen[k];
-        r += rlen[k] != 0;
-    }
-    if (threadIdx.x == 1023) {
-        status[PGL_ST_BYTES] = sh[1023];
-        status[PGL_ST_ROWS] = shn[1023];
-        if (sh[1023] > out_cap) atomicOr(reinterpret_cast<unsigned long long *>(status + PGL_ST_BITS), (unsigned long long)PG_ST_OVERFLOW);
-    }
-}
-
-int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->eig.configured, who, "pg_eig_dev_config"); }
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c ? &c->eig : nullptr, who, "pg_eig_dev_config"); }
 
 EigArgs eig_args(pg_ctx *c, int slot) {
     pg_ctx::EigDev &D = c->eig;
@@ -200,6 +165,15 @@ int queue_render(pg_ctx *c, int slot, hipStream_t st) {
     hipLaunchKernelGGL((k_eig_lines<1>), dim3((unsigned)E.L.n_lines), dim3(64), (size_t)D.cfg.n_cols * 4, st, A, D.cfg);
     HIPCHK(hipGetLastError());
     return pg_line_parse_end(c, E, st);
+}
+
+// .snp rows longer than their room: room for `need` bytes of them, both rows' text once more
+int render_again(pg_ctx *c, int slot, int64_t need, hipStream_t st) {
+    pg_ctx::EigDev::Slot &E = c->eig.s[slot];
+    int rc = E.snp.ensure_roomy((size_t)need + 4096);
+    if (rc != PG_OK) return rc;
+    E.snp_cap = (int64_t)E.snp.cap;
+    return queue_render(c, slot, st);
 }
 
 }  // namespace
@@ -258,9 +232,7 @@ extern "C" int pg_eig_dev_config(pg_ctx *c, const pg_eig_cfg *cfg, const int32_t
 // A block of whole lines (the last byte a line feed, else the block is the host's) into text slot `slot`
 extern "C" int pg_eig_dev_submit(pg_ctx *c, int slot, const char *text, int64_t len) {
     int rc = check_slot(c, slot, "pg_eig_dev_submit");
-    if (rc != PG_OK) return rc;
-    if ((!text && len) || len < 0) return pg_fail(PG_ERR_ARG, "pg_eig_dev_submit: no text");
-    return pg_line_submit_text(c, slot, c->eig.s[slot], text, -1, 0, len, len > 0 && text[len - 1] == '\n');
+    return rc != PG_OK ? rc : pg_line_submit_plain(c, slot, c->eig.s[slot], text, len, "pg_eig_dev_submit");
 }
 
 // The same for a block that is still bgzipped: the members cross PCIe deflated, k_inflate writes their text behind `head` in the slot
@@ -300,11 +272,11 @@ extern "C" int pg_eig_dev_parse(pg_ctx *c, int slot, int64_t first_site, int64_t
     E.snp_cap = std::max<int64_t>(E.snp_cap, n_lines * 32 + 256);
     if ((rc = E.snp.ensure_roomy((size_t)E.snp_cap)) != PG_OK) return rc;
     E.snp_cap = (int64_t)E.snp.cap;
-    HIPCHK(hipMemcpyAsync(E.status.p, E.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
+    if ((rc = pg_line_status_upload(E, st)) != PG_OK) return rc;
     const EigArgs A = eig_args(c, slot);
     hipLaunchKernelGGL((k_eig_lines<0>), dim3((unsigned)n_lines), dim3(64), (size_t)D.cfg.n_cols * 4, st, A, D.cfg);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_eig_scan, dim3(1), dim3(1024), 0, st, E.rlen.p, n_lines, E.roff.p, E.rank.p, A.status, E.snp_cap);
+    pg_rows_scan_queue(st, E.rlen.p, n_lines, E.roff.p, A.status, E.snp_cap, E.rank.p);
     if ((rc = queue_render(c, slot, st)) != PG_OK) return rc;
     ++D.blocks;
     return PG_OK;
@@ -317,52 +289,27 @@ extern "C" int pg_eig_dev_collect(pg_ctx *c, int slot, int64_t *snp_len_out, int
     int rc = check_slot(c, slot, "pg_eig_dev_collect");
     if (rc != PG_OK) return rc;
     if (!snp_len_out || !n_rows_out || !host_line_out) return pg_fail(PG_ERR_ARG, "pg_eig_dev_collect: null argument");
-    pg_ctx::EigDev::Slot &E = c->eig.s[slot];
-    *snp_len_out = *n_rows_out = 0;
-    *host_line_out = -1;
-    if (n_lines_out) *n_lines_out = 0;
-    const bool empty = E.L.state == PGL_EMPTY;
-    if ((rc = pg_line_collect_wait(c, slot, E, "pg_eig_dev_collect")) != PG_OK || empty) return rc;
-    if (n_lines_out) *n_lines_out = E.L.n_lines;
-    if (E.h_status.p[PGL_ST_BITS] == PG_ST_OVERFLOW) {           // only the .snp rows' room: grow it, render again
-        hipStream_t st = c->stream_up;
-        if ((rc = E.snp.ensure_roomy((size_t)E.h_status.p[PGL_ST_BYTES] + 4096)) != PG_OK) return rc;
-        E.snp_cap = (int64_t)E.snp.cap;
-        E.h_status.p[PGL_ST_BITS] = 0;
-        HIPCHK(hipMemcpyAsync(E.status.p, E.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
-        if ((rc = queue_render(c, slot, st)) != PG_OK) return rc;
-        HIPCHK(hipEventSynchronize(E.done));
-        E.L.state = PGL_IDLE;
-    }
-    const PgLineResult R = pgl_decode(E.h_status.p, false);
+    PgLineResult R;
+    rc = pg_line_collect(c, slot, c->eig, c->eig.s[slot], false, render_again, n_lines_out, &R, "pg_eig_dev_collect");
     *host_line_out = R.host_line;
     *snp_len_out = R.bytes;
     *n_rows_out = R.rows;
-    if (R.host_block) ++c->eig.host_blocks;
-    return PG_OK;
+    return rc;
 }
 
 extern "C" int pg_eig_dev_rows(pg_ctx *c, int slot, int which, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_eig_dev_rows");
     if (rc != PG_OK) return rc;
-    pg_ctx::EigDev::Slot &E = c->eig.s[slot];
-    DevBuf<uint8_t> &B = which ? E.snp : E.geno;
-    if (which < 0 || which > 1 || len < 0 || (len && !dst) || (size_t)len > B.cap) return pg_fail(PG_ERR_ARG, "pg_eig_dev_rows: bad length");
-    return len ? pg_copy_back(c, dst, B.p, len) : PG_OK;
+    if (which < 0 || which > 1) return pg_fail(PG_ERR_ARG, "pg_eig_dev_rows: bad length");
+    return pg_line_rows(c, which ? c->eig.s[slot].snp : c->eig.s[slot].geno, dst, len, "pg_eig_dev_rows: bad length");
 }
 
 // the text of the collected block -> dst (a block that goes to the host route and whose text the host never had: BGZF)
 extern "C" int pg_eig_dev_text(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_eig_dev_text");
-    if (rc != PG_OK) return rc;
-    pg_ctx::TokSlot &T = c->tok[slot];
-    if (len < 0 || (len && !dst) || len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_eig_dev_text: bad length");
-    return len ? pg_copy_back(c, dst, T.tp, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_text(c, slot, 0, len, dst, "pg_eig_dev_text: bad length");
 }
 
 extern "C" int pg_eig_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out) {
-    if (!c || !blocks_out || !host_blocks_out) return pg_fail(PG_ERR_ARG, "pg_eig_dev_stats: null argument");
-    *blocks_out = c->eig.blocks;
-    *host_blocks_out = c->eig.host_blocks;
-    return PG_OK;
+    return pg_line_stats(c ? &c->eig : nullptr, blocks_out, host_blocks_out, "pg_eig_dev_stats");
 }

@@ -7,7 +7,7 @@
 //                    a lane per selected column classifies its cells, the sums reduced across the wave, siteTest; the line's flags,
 //                    its position (thinning) and its row's size
 //   k_filt_thin      (--thinDist only) a lane per pod walks its lines in order over the flags and positions (filterGenotypes.py:41-55)
-//   scan             the rows' places (k_vcf_scan, pg_vcf_dev.hip)
+//   scan             the rows' places (k_rows_scan, pg_line_slot.hip)
 //   k_filt_lines<1>  a wavefront per written line: the first two fields copied, the cells rendered, placed by a wave scan of their sizes
 // The text arrives in the tokenizer's text slot with its line feeds listed (pg_tok_text_submit / pg_tok_lines).  A line outside the
 // regular spelling, or one on which the reference raises, hands the BLOCK to the host route (pg_filter_dev_collect reports the line).
@@ -18,10 +18,6 @@
 
 #include <algorithm>
 #include <cstring>
-
-int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
-                     const long long *status_d, long long *comp_total_d);
-void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
 
 namespace {
 
@@ -224,7 +220,7 @@ __global__ __launch_bounds__(64) void k_filt_thin(FiltArgs A, PgfConfig cfg) {
     }
 }
 
-int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->filt.configured, who, "pg_filter_dev_config"); }
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c ? &c->filt : nullptr, who, "pg_filter_dev_config"); }
 
 }  // namespace
 
@@ -346,6 +342,15 @@ int queue_render(pg_ctx *c, int slot, hipStream_t st) {
     return pg_line_parse_end(c, F, st);
 }
 
+// rows longer than their room: room for `need` bytes of them (k_deflate reads 32 bytes past the rows), rendered once more
+int render_again(pg_ctx *c, int slot, int64_t need, hipStream_t st) {
+    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
+    int rc = F.out.ensure_roomy((size_t)need + 4096 + 64);
+    if (rc != PG_OK) return rc;
+    F.out_cap = (int64_t)F.out.cap - 64;
+    return queue_render(c, slot, st);
+}
+
 }  // namespace
 
 // Queues the kernels of the block in `slot` (waits for the number of its lines only)
@@ -367,7 +372,7 @@ extern "C" int pg_filter_dev_parse(pg_ctx *c, int slot) {
     F.out_cap = std::max<int64_t>(F.out_cap, T.len + n_lines * 16 + 4096);
     if ((rc = F.out.ensure_roomy((size_t)F.out_cap + 64)) != PG_OK) return rc;
     F.out_cap = (int64_t)F.out.cap - 64;                          // (k_deflate reads 32 bytes past the rows)
-    HIPCHK(hipMemcpyAsync(F.status.p, F.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
+    if ((rc = pg_line_status_upload(F, st)) != PG_OK) return rc;
     const FiltArgs A = filt_args(c, slot);
     hipLaunchKernelGGL((k_filt_lines<0>), dim3((unsigned)n_lines), dim3(64), filt_lds(D.cfg), st, A, D.cfg);
     if (D.cfg.thin_dist) {
@@ -388,62 +393,31 @@ extern "C" int pg_filter_dev_collect(pg_ctx *c, int slot, int64_t *rows_len_out,
     int rc = check_slot(c, slot, "pg_filter_dev_collect");
     if (rc != PG_OK) return rc;
     if (!rows_len_out || !n_rows_out || !host_line_out) return pg_fail(PG_ERR_ARG, "pg_filter_dev_collect: null argument");
-    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
-    *rows_len_out = *n_rows_out = 0;
-    *host_line_out = -1;
-    if (bgzf_len_out) *bgzf_len_out = 0;
-    if (n_lines_out) *n_lines_out = 0;
-    const bool empty = F.L.state == PGL_EMPTY;
-    if ((rc = pg_line_collect_wait(c, slot, F, "pg_filter_dev_collect")) != PG_OK || empty) return rc;
-    if (n_lines_out) *n_lines_out = F.L.n_lines;
-    if (F.h_status.p[PGL_ST_BITS] == PG_ST_OVERFLOW) {           // only the rows' room: grow it, render again
-        hipStream_t st = c->stream_up;
-        if ((rc = F.out.ensure_roomy((size_t)F.h_status.p[PGL_ST_BYTES] + 4096 + 64)) != PG_OK) return rc;
-        F.out_cap = (int64_t)F.out.cap - 64;
-        F.h_status.p[PGL_ST_BITS] = 0;
-        F.h_status.p[PGL_ST_BGZF_BYTES] = 0;
-        HIPCHK(hipMemcpyAsync(F.status.p, F.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
-        if ((rc = queue_render(c, slot, st)) != PG_OK) return rc;
-        HIPCHK(hipEventSynchronize(F.done));
-        F.L.state = PGL_IDLE;
-    }
-    const PgLineResult R = pgl_decode(F.h_status.p, c->filt.bgzf_rows);
+    PgLineResult R;
+    rc = pg_line_collect(c, slot, c->filt, c->filt.s[slot], c->filt.bgzf_rows, render_again, n_lines_out, &R, "pg_filter_dev_collect");
     *host_line_out = R.host_line;
     *rows_len_out = R.bytes;
     *n_rows_out = R.rows;
     if (bgzf_len_out) *bgzf_len_out = R.bgzf_bytes;
-    if (R.host_block) ++c->filt.host_blocks;
-    return PG_OK;
+    return rc;
 }
 
 extern "C" int pg_filter_dev_rows(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_filter_dev_rows");
-    if (rc != PG_OK) return rc;
-    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
-    if (len < 0 || (len && !dst) || (size_t)len > F.out.cap) return pg_fail(PG_ERR_ARG, "pg_filter_dev_rows: bad length");
-    return len ? pg_copy_back(c, dst, F.out.p, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_rows(c, c->filt.s[slot].out, dst, len, "pg_filter_dev_rows: bad length");
 }
 
 extern "C" int pg_filter_dev_rows_bgzf(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_filter_dev_rows_bgzf");
-    if (rc != PG_OK) return rc;
-    pg_ctx::FiltDev::Slot &F = c->filt.s[slot];
-    if (len < 0 || (len && !dst) || (size_t)len > F.df.comp.cap) return pg_fail(PG_ERR_ARG, "pg_filter_dev_rows_bgzf: bad length");
-    return len ? pg_copy_back(c, dst, F.df.comp.p, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_rows(c, c->filt.s[slot].df.comp, dst, len, "pg_filter_dev_rows_bgzf: bad length");
 }
 
 // the text of the collected block -> dst (a block that goes to the host route and whose text the host never had: BGZF)
 extern "C" int pg_filter_dev_text(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_filter_dev_text");
-    if (rc != PG_OK) return rc;
-    pg_ctx::TokSlot &T = c->tok[slot];
-    if (len < 0 || (len && !dst) || len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_filter_dev_text: bad length");
-    return len ? pg_copy_back(c, dst, T.tp, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_text(c, slot, 0, len, dst, "pg_filter_dev_text: bad length");
 }
 
 extern "C" int pg_filter_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out) {
-    if (!c || !blocks_out || !host_blocks_out) return pg_fail(PG_ERR_ARG, "pg_filter_dev_stats: null argument");
-    *blocks_out = c->filt.blocks;
-    *host_blocks_out = c->filt.host_blocks;
-    return PG_OK;
+    return pg_line_stats(c ? &c->filt : nullptr, blocks_out, host_blocks_out, "pg_filter_dev_stats");
 }

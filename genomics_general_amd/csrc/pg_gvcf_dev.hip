@@ -7,7 +7,7 @@
 //                    selected columns classify their cells, the four base counts and the cells' bytes reduced across the wave; with -r
 //                    the scaffold's hash summed a lane a byte and looked up in the table over the fasta's names, the base read; the
 //                    alleles ordered (pgg_alleles); the row's size
-//   scan             the rows' places (k_vcf_scan, pg_vcf_dev.hip)
+//   scan             the rows' places (k_rows_scan, pg_line_slot.hip)
 //   k_gvcf_lines<1>  the same walk for a written line, then: CHROM \t POS copied, ID .. FORMAT written, the cells coded and placed by
 //                    a wave scan of their sizes
 // The text arrives in the tokenizer's text slot with its line feeds listed (pg_line_slot.h: submit, parse, collect).  A line outside
@@ -19,10 +19,6 @@
 
 #include <algorithm>
 #include <cstring>
-
-int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
-                     const long long *status_d, long long *comp_total_d);
-void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
 
 namespace {
 
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(64) void k_gvcf_lines(GvcfArgs A, PggConfig cfg) {
     if (lane == 0) o[at] = '\n';
 }
 
-int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->gvcf.configured, who, "pg_gvcf_dev_config"); }
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c ? &c->gvcf : nullptr, who, "pg_gvcf_dev_config"); }
 
 }  // namespace
 
@@ -183,9 +179,7 @@ extern "C" int pg_gvcf_dev_config(pg_ctx *c, const pg_gvcf_cfg *cfg, const int32
 // A block of whole lines (the last byte a line feed, else the block is the host's) into text slot `slot`
 extern "C" int pg_gvcf_dev_submit(pg_ctx *c, int slot, const char *text, int64_t len) {
     int rc = check_slot(c, slot, "pg_gvcf_dev_submit");
-    if (rc != PG_OK) return rc;
-    if ((!text && len) || len < 0) return pg_fail(PG_ERR_ARG, "pg_gvcf_dev_submit: no text");
-    return pg_line_submit_text(c, slot, c->gvcf.s[slot], text, -1, 0, len, len > 0 && text[len - 1] == '\n');
+    return rc != PG_OK ? rc : pg_line_submit_plain(c, slot, c->gvcf.s[slot], text, len, "pg_gvcf_dev_submit");
 }
 
 // The same for a block that is still bgzipped: the members cross PCIe deflated, k_inflate writes their text behind `head` in the slot
@@ -243,6 +237,15 @@ int queue_render(pg_ctx *c, int slot, hipStream_t st) {
     return pg_line_parse_end(c, G, st);
 }
 
+// rows longer than their room: room for `need` bytes of them (k_deflate reads 32 bytes past the rows), rendered once more
+int render_again(pg_ctx *c, int slot, int64_t need, hipStream_t st) {
+    pg_ctx::GvcfDev::Slot &G = c->gvcf.s[slot];
+    int rc = G.out.ensure_roomy((size_t)need + 4096 + 64);
+    if (rc != PG_OK) return rc;
+    G.out_cap = (int64_t)G.out.cap - 64;
+    return queue_render(c, slot, st);
+}
+
 }  // namespace
 
 // Queues the kernels of the block in `slot` (waits for the number of its lines only)
@@ -263,7 +266,7 @@ extern "C" int pg_gvcf_dev_parse(pg_ctx *c, int slot) {
     G.out_cap = std::max<int64_t>(G.out_cap, T.len + n_lines * 32 + 4096);
     if ((rc = G.out.ensure_roomy((size_t)G.out_cap + 64)) != PG_OK) return rc;
     G.out_cap = (int64_t)G.out.cap - 64;                          // (k_deflate reads 32 bytes past the rows)
-    HIPCHK(hipMemcpyAsync(G.status.p, G.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
+    if ((rc = pg_line_status_upload(G, st)) != PG_OK) return rc;
     const GvcfArgs A = gvcf_args(c, slot);
     hipLaunchKernelGGL((k_gvcf_lines<0>), dim3((unsigned)n_lines), dim3(64), (size_t)D.cfg.n_cols * 4, st, A, D.cfg);
     HIPCHK(hipGetLastError());
@@ -281,62 +284,31 @@ extern "C" int pg_gvcf_dev_collect(pg_ctx *c, int slot, int64_t *rows_len_out, i
     int rc = check_slot(c, slot, "pg_gvcf_dev_collect");
     if (rc != PG_OK) return rc;
     if (!rows_len_out || !n_rows_out || !host_line_out) return pg_fail(PG_ERR_ARG, "pg_gvcf_dev_collect: null argument");
-    pg_ctx::GvcfDev::Slot &G = c->gvcf.s[slot];
-    *rows_len_out = *n_rows_out = 0;
-    *host_line_out = -1;
-    if (bgzf_len_out) *bgzf_len_out = 0;
-    if (n_lines_out) *n_lines_out = 0;
-    const bool empty = G.L.state == PGL_EMPTY;
-    if ((rc = pg_line_collect_wait(c, slot, G, "pg_gvcf_dev_collect")) != PG_OK || empty) return rc;
-    if (n_lines_out) *n_lines_out = G.L.n_lines;
-    if (G.h_status.p[PGL_ST_BITS] == PG_ST_OVERFLOW) {           // only the rows' room: grow it, render again
-        hipStream_t st = c->stream_up;
-        if ((rc = G.out.ensure_roomy((size_t)G.h_status.p[PGL_ST_BYTES] + 4096 + 64)) != PG_OK) return rc;
-        G.out_cap = (int64_t)G.out.cap - 64;
-        G.h_status.p[PGL_ST_BITS] = 0;
-        G.h_status.p[PGL_ST_BGZF_BYTES] = 0;
-        HIPCHK(hipMemcpyAsync(G.status.p, G.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
-        if ((rc = queue_render(c, slot, st)) != PG_OK) return rc;
-        HIPCHK(hipEventSynchronize(G.done));
-        G.L.state = PGL_IDLE;
-    }
-    const PgLineResult R = pgl_decode(G.h_status.p, c->gvcf.bgzf_rows);
+    PgLineResult R;
+    rc = pg_line_collect(c, slot, c->gvcf, c->gvcf.s[slot], c->gvcf.bgzf_rows, render_again, n_lines_out, &R, "pg_gvcf_dev_collect");
     *host_line_out = R.host_line;
     *rows_len_out = R.bytes;
     *n_rows_out = R.rows;
     if (bgzf_len_out) *bgzf_len_out = R.bgzf_bytes;
-    if (R.host_block) ++c->gvcf.host_blocks;
-    return PG_OK;
+    return rc;
 }
 
 extern "C" int pg_gvcf_dev_rows(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_gvcf_dev_rows");
-    if (rc != PG_OK) return rc;
-    pg_ctx::GvcfDev::Slot &G = c->gvcf.s[slot];
-    if (len < 0 || (len && !dst) || (size_t)len > G.out.cap) return pg_fail(PG_ERR_ARG, "pg_gvcf_dev_rows: bad length");
-    return len ? pg_copy_back(c, dst, G.out.p, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_rows(c, c->gvcf.s[slot].out, dst, len, "pg_gvcf_dev_rows: bad length");
 }
 
 extern "C" int pg_gvcf_dev_rows_bgzf(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_gvcf_dev_rows_bgzf");
-    if (rc != PG_OK) return rc;
-    pg_ctx::GvcfDev::Slot &G = c->gvcf.s[slot];
-    if (len < 0 || (len && !dst) || (size_t)len > G.df.comp.cap) return pg_fail(PG_ERR_ARG, "pg_gvcf_dev_rows_bgzf: bad length");
-    return len ? pg_copy_back(c, dst, G.df.comp.p, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_rows(c, c->gvcf.s[slot].df.comp, dst, len, "pg_gvcf_dev_rows_bgzf: bad length");
 }
 
 // the text of the collected block -> dst (a block that goes to the host route and whose text the host never had: BGZF)
 extern "C" int pg_gvcf_dev_text(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_gvcf_dev_text");
-    if (rc != PG_OK) return rc;
-    pg_ctx::TokSlot &T = c->tok[slot];
-    if (len < 0 || (len && !dst) || len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_gvcf_dev_text: bad length");
-    return len ? pg_copy_back(c, dst, T.tp, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_text(c, slot, 0, len, dst, "pg_gvcf_dev_text: bad length");
 }
 
 extern "C" int pg_gvcf_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out) {
-    if (!c || !blocks_out || !host_blocks_out) return pg_fail(PG_ERR_ARG, "pg_gvcf_dev_stats: null argument");
-    *blocks_out = c->gvcf.blocks;
-    *host_blocks_out = c->gvcf.host_blocks;
-    return PG_OK;
+    return pg_line_stats(c ? &c->gvcf : nullptr, blocks_out, host_blocks_out, "pg_gvcf_dev_stats");
 }

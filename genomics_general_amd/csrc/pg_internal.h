@@ -118,7 +118,12 @@ void pg_launch_popstats(hipStream_t st, const double *sums, const int64_t *cnts,
 
 // ---- a block of whole lines through one of the tokenizer's two text slots ---------------------------------
 struct pg_ctx;
-struct PgLineDev;               // pg_ctx::LineSlot (pg_ctx.h)
+struct PgLineDev;               // pg_ctx::LineSlot, PgLineRoute, PgDeflate, DevBuf: pg_ctx.h
+struct PgLineRoute;
+struct PgLineResult;
+struct PgDeflate;
+template <class T>
+struct DevBuf;
 // pg_tokenize.hip: the text (or its deflated members) to the device, line feeds counted behind it; the wait for the count, the line
 // feeds' positions queued; the members' checksums of a block whose kernels have finished
 int pg_tok_text_submit(pg_ctx *c, int slot, const char *text, int fd, int64_t file_offset, int64_t len);
@@ -127,13 +132,24 @@ int pg_tok_bgzf_submit(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_le
                        int64_t text_len, int64_t line_len_hint);
 int pg_tok_lines(pg_ctx *c, int slot, int64_t *n_lines_out);
 int pg_tok_crc_result(pg_ctx *c, int slot);
+// pg_deflate.hip: the *total_d bytes of text at text_d (max_text at most) as BGZF members into D.comp, their bytes into *comp_total_d,
+// queued on st; status_d (may be null): status words that cancel it when raised
+int pg_deflate_queue(pg_ctx *c, hipStream_t st, PgDeflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
+                     const long long *status_d, long long *comp_total_d);
 // pg_line_slot.hip: the protocol of pg_line_slot.h carried out for the per-line routes (`who`: the entry point, for the error texts).
 // c->tok_small, made on first use
 int pg_small_stream(pg_ctx *c);
 // len bytes device -> host on the small stream (beside the next block's kernels on the copy stream), waited for
 int pg_copy_back(pg_ctx *c, void *dst, const void *src, int64_t len);
-int pg_line_check_slot(pg_ctx *c, int slot, bool configured, const char *who, const char *config_name);
+// k_rows_scan queued on st: roff = the exclusive sums of rlen over the lines, rank (may be null) = those of rlen != 0; their totals into
+// status[PGL_ST_BYTES] and [PGL_ST_ROWS], PG_ST_OVERFLOW raised when the bytes exceed out_cap
+void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap,
+                        int64_t *rank = nullptr);
+// D: the route's part of the context, null with a null context
+int pg_line_check_slot(pg_ctx *c, int slot, const PgLineRoute *D, const char *who, const char *config_name);
 int pg_line_submit_text(pg_ctx *c, int slot, PgLineDev &S, const char *text, int fd, int64_t file_offset, int64_t len, bool last_is_newline);
+// ... of text in memory, its arguments checked and its last byte read here
+int pg_line_submit_plain(pg_ctx *c, int slot, PgLineDev &S, const char *text, int64_t len, const char *who);
 // last_known = false: whether the text ends in a line feed is read on the device in parse (a stream synchronisation more)
 int pg_line_submit_bgzf(pg_ctx *c, int slot, PgLineDev &S, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off,
                         const uint32_t *in_len, const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head,
@@ -141,10 +157,23 @@ int pg_line_submit_bgzf(pg_ctx *c, int slot, PgLineDev &S, const uint8_t *comp, 
 // everything of parse in front of the route's kernels.  *nothing_out: there is nothing for the route to queue (an empty block --
 // S.L.state stays PGL_EMPTY --, or one that is the host's as it stands -- queued, S.done recorded)
 int pg_line_parse_begin(pg_ctx *c, int slot, PgLineDev &S, int64_t *n_lines_out, bool *nothing_out, const char *who);
+// the host's status words to the device on `st`
+int pg_line_status_upload(PgLineDev &S, hipStream_t st);
 // behind the route's kernels: the status words back on `st`, S.done recorded there, queued
 int pg_line_parse_end(pg_ctx *c, PgLineDev &S, hipStream_t st);
 // the head of collect: the state checked, S.done waited for, idle, the members' checksums.  An empty block: idle, nothing else
 int pg_line_collect_wait(pg_ctx *c, int slot, PgLineDev &S, const char *who);
+// a route's second render: its row buffer grown for `need` bytes of rows, its render kernels and pg_line_parse_end queued on st
+typedef int (*PgLineAgain)(pg_ctx *c, int slot, int64_t need, hipStream_t st);
+// all of collect but the route's out-parameters: the wait, *n_lines_out (may be null; 0 for an empty block), rows that outgrew their
+// room rendered once more by `again` (null: the route's rows cannot) and waited for, the status words decoded into *R (bgzf_rows: the
+// fifth word counts), a host block counted in D
+int pg_line_collect(pg_ctx *c, int slot, PgLineRoute &D, PgLineDev &S, bool bgzf_rows, PgLineAgain again, int64_t *n_lines_out,
+                    PgLineResult *R, const char *who);
+// bytes [off, off + len) of the slot's text / the first len bytes of a row buffer -> dst; `bad`: the error's text
+int pg_line_text(pg_ctx *c, int slot, int64_t off, int64_t len, uint8_t *dst, const char *bad);
+int pg_line_rows(pg_ctx *c, const DevBuf<uint8_t> &B, uint8_t *dst, int64_t len, const char *bad);
+int pg_line_stats(const PgLineRoute *D, int64_t *blocks_out, int64_t *host_blocks_out, const char *who);
 
 // ---- shared device routines ---------------------------------------------------------------------------
 // float64 sum in the order NumPy's add.reduce visits a contiguous array, by one lane (k_hapstats: the reference's

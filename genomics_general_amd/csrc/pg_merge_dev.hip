@@ -17,7 +17,7 @@
 //   k_merge_lines  the sparse methods, a thread per line of the candidate files: binary searches in the other files' keys give the
 //   k_merge_pos    presence mask and the line's place in the merged order; the dense methods, a thread per position of the range.
 //                  Rule 3, then the length of the written line (0: nothing is written)
-//   scan           the lines' places (k_vcf_scan, pg_vcf_dev.hip)
+//   scan           the lines' places (k_rows_scan, pg_line_slot.hip)
 //   k_merge_emit   a wavefront per written line: a lane per file finds the file's line, then the head (copied from the text, or the
 //                  .fai's name and the position rendered) and every file's cells or dummy cells, 64 consecutive bytes a step, tabs
 //                  turned into the separator.  Plain vector stores
@@ -34,9 +34,6 @@ int pg_tok_bgzf_submit(pg_ctx *c, int slot, const uint8_t *comp, int64_t comp_le
                        const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
                        int64_t text_len, int64_t line_len_hint);
 int pg_tok_crc_result(pg_ctx *c, int slot);
-int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
-                     const long long *status_d, long long *comp_total_d);
-void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
 
 namespace {
 

@@ -7,7 +7,7 @@
 //   k_ped_lines  a wavefront per line: '#' lines marked, the line's tabs ranked by ballots into LDS, the field count against the
 //                header's, lanes strided over the selected columns check their cell's length against the sample's (and its letter
 //                under -f diplo), the position, whether the scaffold differs from the site's before, the .map row's size
-//   scans        the kept lines' row indices, the .map rows' places (k_vcf_scan, pg_vcf_dev.hip)
+//   scans        the kept lines' row indices, the .map rows' places (k_rows_scan, pg_line_slot.hip)
 //   k_ped_map    a wavefront per kept line: its record at its row (where the line begins, the run flag), its .map row
 //   k_ped_tile   the transpose: a workgroup takes PGP_TILE_LINES consecutive sites and a tile of samples; each of its waves reads a
 //                line in 64-byte steps, ranks its tabs, a lane per sample expands the sample's cell into its 2 a_q bytes (allele,
@@ -23,8 +23,6 @@
 
 #include <algorithm>
 #include <cstring>
-
-void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
 
 namespace {
 
@@ -208,7 +206,7 @@ __global__ __launch_bounds__(PGP_TILE_THREADS) void k_ped_tile(PedArgs A, PgpCon
     }
 }
 
-int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->ped.configured, who, "pg_ped_dev_config"); }
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c ? &c->ped : nullptr, who, "pg_ped_dev_config"); }
 
 PedArgs ped_args(pg_ctx *c, int slot) {
     pg_ctx::PedDev &D = c->ped;
@@ -287,9 +285,7 @@ extern "C" int pg_ped_dev_config(pg_ctx *c, const pg_ped_cfg *cfg, const int32_t
 // A block of whole lines (the last byte a line feed, else the block is the host's) into text slot `slot`
 extern "C" int pg_ped_dev_submit(pg_ctx *c, int slot, const char *text, int64_t len) {
     int rc = check_slot(c, slot, "pg_ped_dev_submit");
-    if (rc != PG_OK) return rc;
-    if ((!text && len) || len < 0) return pg_fail(PG_ERR_ARG, "pg_ped_dev_submit: no text");
-    return pg_line_submit_text(c, slot, c->ped.s[slot], text, -1, 0, len, len > 0 && text[len - 1] == '\n');
+    return rc != PG_OK ? rc : pg_line_submit_plain(c, slot, c->ped.s[slot], text, len, "pg_ped_dev_submit");
 }
 
 // The same for a block that is still bgzipped: the members cross PCIe deflated, k_inflate writes their text behind `head` in the slot
@@ -322,6 +318,15 @@ int queue_map(pg_ctx *c, int slot, hipStream_t st, bool first) {
     return pg_line_parse_end(c, P, st);
 }
 
+// .map rows longer than their room: room for `need` bytes of them, written once more (the matrix stands)
+int map_again(pg_ctx *c, int slot, int64_t need, hipStream_t st) {
+    pg_ctx::PedDev::Slot &P = c->ped.s[slot];
+    int rc = P.map.ensure_roomy((size_t)need + 4096);
+    if (rc != PG_OK) return rc;
+    P.map_cap = (int64_t)P.map.cap;
+    return queue_map(c, slot, st, false);
+}
+
 }  // namespace
 
 // Queues the kernels of the block in `slot` (waits for the number of its lines only)
@@ -348,7 +353,7 @@ extern "C" int pg_ped_dev_parse(pg_ctx *c, int slot) {
     P.map_cap = std::max<int64_t>(P.map_cap, n_lines * 32 + 256);
     if ((rc = P.map.ensure_roomy((size_t)P.map_cap)) != PG_OK) return rc;
     P.map_cap = (int64_t)P.map.cap;
-    HIPCHK(hipMemcpyAsync(P.status.p, P.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
+    if ((rc = pg_line_status_upload(P, st)) != PG_OK) return rc;
     const PedArgs A = ped_args(c, slot);
     hipLaunchKernelGGL(k_ped_lines, dim3((unsigned)n_lines), dim3(64), (size_t)D.cfg.n_cols * 4, st, A, D.cfg);
     HIPCHK(hipGetLastError());
@@ -370,41 +375,22 @@ extern "C" int pg_ped_dev_collect(pg_ctx *c, int slot, int64_t *n_sites_out, int
     if (rc != PG_OK) return rc;
     if (!n_sites_out || !map_len_out || !host_line_out) return pg_fail(PG_ERR_ARG, "pg_ped_dev_collect: null argument");
     pg_ctx::PedDev::Slot &P = c->ped.s[slot];
-    *n_sites_out = *map_len_out = 0;
-    *host_line_out = -1;
-    if (n_lines_out) *n_lines_out = 0;
-    if (pitch_out) *pitch_out = 0;
     const bool empty = P.L.state == PGL_EMPTY;
-    if ((rc = pg_line_collect_wait(c, slot, P, "pg_ped_dev_collect")) != PG_OK || empty) return rc;
-    if (n_lines_out) *n_lines_out = P.L.n_lines;
-    if (pitch_out) *pitch_out = P.pitch;
-    if (P.h_status.p[PGL_ST_BITS] == PG_ST_OVERFLOW) {           // only the .map rows' room: grow it, write them again
-        hipStream_t st = c->stream_up;
-        if ((rc = P.map.ensure_roomy((size_t)P.h_status.p[PGL_ST_BYTES] + 4096)) != PG_OK) return rc;
-        P.map_cap = (int64_t)P.map.cap;
-        P.h_status.p[PGL_ST_BITS] = 0;
-        HIPCHK(hipMemcpyAsync(P.status.p, P.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
-        if ((rc = queue_map(c, slot, st, false)) != PG_OK) return rc;
-        HIPCHK(hipEventSynchronize(P.done));
-        P.L.state = PGL_IDLE;
-    }
-    const PgLineResult R = pgl_decode(P.h_status.p, false);
+    PgLineResult R;
+    rc = pg_line_collect(c, slot, c->ped, P, false, map_again, n_lines_out, &R, "pg_ped_dev_collect");
+    if (pitch_out) *pitch_out = rc == PG_OK && !empty ? P.pitch : 0;
     *host_line_out = R.host_line;
     *map_len_out = R.bytes;
     *n_sites_out = R.rows;
-    if (R.host_block) ++c->ped.host_blocks;
-    return PG_OK;
+    return rc;
 }
 
 // which = 0: the first len bytes of the matrix (sample q's row at woff[q] x pitch); 1: the .map rows
 extern "C" int pg_ped_dev_rows(pg_ctx *c, int slot, int which, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_ped_dev_rows");
     if (rc != PG_OK) return rc;
-    pg_ctx::PedDev::Slot &P = c->ped.s[slot];
     if (which < 0 || which > 1) return pg_fail(PG_ERR_ARG, "pg_ped_dev_rows: bad output");
-    DevBuf<uint8_t> &B = which ? P.map : P.out;
-    if (len < 0 || (len && !dst) || (size_t)len > B.cap) return pg_fail(PG_ERR_ARG, "pg_ped_dev_rows: bad length");
-    return len ? pg_copy_back(c, dst, B.p, len) : PG_OK;
+    return pg_line_rows(c, which ? c->ped.s[slot].map : c->ped.s[slot].out, dst, len, "pg_ped_dev_rows: bad length");
 }
 
 // per site of the collected block: 1 where its scaffold differs from the site's before, where its line begins in the text
@@ -425,10 +411,7 @@ extern "C" int pg_ped_dev_meta(pg_ctx *c, int slot, uint8_t *run_dst, int64_t *s
 // host never had its text: BGZF)
 extern "C" int pg_ped_dev_text(pg_ctx *c, int slot, int64_t off, int64_t len, uint8_t *dst) {
     int rc = check_slot(c, slot, "pg_ped_dev_text");
-    if (rc != PG_OK) return rc;
-    pg_ctx::TokSlot &T = c->tok[slot];
-    if (off < 0 || len < 0 || (len && !dst) || off + len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_ped_dev_text: bad range");
-    return len ? pg_copy_back(c, dst, T.tp + off, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_text(c, slot, off, len, dst, "pg_ped_dev_text: bad range");
 }
 
 extern "C" int pg_ped_dev_tile_seqs(pg_ctx *c, int *tile_seqs_out) {
@@ -438,8 +421,5 @@ extern "C" int pg_ped_dev_tile_seqs(pg_ctx *c, int *tile_seqs_out) {
 }
 
 extern "C" int pg_ped_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out) {
-    if (!c || !blocks_out || !host_blocks_out) return pg_fail(PG_ERR_ARG, "pg_ped_dev_stats: null argument");
-    *blocks_out = c->ped.blocks;
-    *host_blocks_out = c->ped.host_blocks;
-    return PG_OK;
+    return pg_line_stats(c ? &c->ped : nullptr, blocks_out, host_blocks_out, "pg_ped_dev_stats");
 }

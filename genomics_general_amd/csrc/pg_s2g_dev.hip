@@ -6,7 +6,7 @@
 // Stage 1, a fasta block in one of the tokenizer's text slots (csrc/pg_line_slot.h):
 //   k_s2g_lines   a wavefront per line, 16 bytes a lane and step: head lines ('>' first) marked, irregular bytes (a blank, a tab or \r in a sequence line, \r,
 //                 a second '>' or text that is not ASCII anywhere) raise the block to the host, the line's residue count
-//   scans         the head lines' ranks, the sequence lines' places in the store (k_vcf_scan, pg_vcf_dev.hip)
+//   scans         the head lines' ranks, the sequence lines' places in the store (k_rows_scan, pg_line_slot.hip)
 //   k_s2g_heads   a thread per line: a head line's record (where it begins, its length, the block's residues in front of it)
 //   k_s2g_gather  a wavefront per sequence line: its bytes to store[base + place], byte stores up to the first multiple of 16 of the
 //                 destination, 16-byte stores behind it
@@ -24,10 +24,6 @@
 #include <algorithm>
 #include <cstring>
 #include <vector>
-
-int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
-                     const long long *status_d, long long *comp_total_d);
-void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
 
 namespace {
 
@@ -192,7 +188,7 @@ __global__ __launch_bounds__(PGS_TILE_THREADS) void k_s2g_tile(S2gTileArgs A) {
     }
 }
 
-int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->s2g.configured, who, "pg_s2g_dev_begin"); }
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c ? &c->s2g : nullptr, who, "pg_s2g_dev_begin"); }
 
 // room for `need` residues in the store, the first `keep` of them kept
 int store_room(pg_ctx *c, int64_t need, int64_t keep) {
@@ -227,9 +223,7 @@ extern "C" int pg_s2g_dev_begin(pg_ctx *c, int64_t store_hint) {
 // A block of whole lines (the last byte a line feed, else the block is the host's) into text slot `slot`
 extern "C" int pg_s2g_dev_submit(pg_ctx *c, int slot, const char *text, int64_t len) {
     int rc = check_slot(c, slot, "pg_s2g_dev_submit");
-    if (rc != PG_OK) return rc;
-    if ((!text && len) || len < 0) return pg_fail(PG_ERR_ARG, "pg_s2g_dev_submit: no text");
-    return pg_line_submit_text(c, slot, c->s2g.s[slot], text, -1, 0, len, len > 0 && text[len - 1] == '\n');
+    return rc != PG_OK ? rc : pg_line_submit_plain(c, slot, c->s2g.s[slot], text, len, "pg_s2g_dev_submit");
 }
 
 // The same for a block that is still bgzipped: the members cross PCIe deflated, k_inflate writes their text behind `head` in the slot
@@ -261,7 +255,7 @@ extern "C" int pg_s2g_dev_parse(pg_ctx *c, int slot, int64_t base, int open) {
     if ((rc = P.cnt.ensure_roomy(nl)) != PG_OK || (rc = P.head.ensure_roomy(nl)) != PG_OK || (rc = P.roff.ensure_roomy(nl)) != PG_OK ||
         (rc = P.hrow.ensure_roomy(nl)) != PG_OK || (rc = P.hrec.ensure_roomy(3 * nl)) != PG_OK)
         return rc;
-    HIPCHK(hipMemcpyAsync(P.status.p, P.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
+    if ((rc = pg_line_status_upload(P, st)) != PG_OK) return rc;
     S2gLineArgs A;
     A.text = T.tp;
     A.nl = T.nl.p;
@@ -296,19 +290,12 @@ extern "C" int pg_s2g_dev_collect(pg_ctx *c, int slot, int64_t *n_res_out, int64
     int rc = check_slot(c, slot, "pg_s2g_dev_collect");
     if (rc != PG_OK) return rc;
     if (!n_res_out || !n_heads_out || !host_line_out) return pg_fail(PG_ERR_ARG, "pg_s2g_dev_collect: null argument");
-    pg_ctx::S2gDev::Slot &P = c->s2g.s[slot];
-    *n_res_out = *n_heads_out = 0;
-    *host_line_out = -1;
-    if (n_lines_out) *n_lines_out = 0;
-    const bool empty = P.L.state == PGL_EMPTY;
-    if ((rc = pg_line_collect_wait(c, slot, P, "pg_s2g_dev_collect")) != PG_OK || empty) return rc;
-    if (n_lines_out) *n_lines_out = P.L.n_lines;
-    const PgLineResult R = pgl_decode(P.h_status.p, true);
+    PgLineResult R;
+    rc = pg_line_collect(c, slot, c->s2g, c->s2g.s[slot], true, nullptr, n_lines_out, &R, "pg_s2g_dev_collect");
     *host_line_out = R.host_line;
     *n_res_out = R.bytes;
     *n_heads_out = R.bgzf_bytes;                                  // (k_s2g_note put the head lines' number there)
-    if (R.host_block) ++c->s2g.host_blocks;
-    return PG_OK;
+    return rc;
 }
 
 // the collected block's head lines, three words each: where the line begins in the text, its bytes, the block's residues in front
@@ -324,10 +311,7 @@ extern "C" int pg_s2g_dev_heads(pg_ctx *c, int slot, int64_t *dst, int64_t n_hea
 // never had its text: BGZF)
 extern "C" int pg_s2g_dev_text(pg_ctx *c, int slot, int64_t off, int64_t len, uint8_t *dst) {
     int rc = check_slot(c, slot, "pg_s2g_dev_text");
-    if (rc != PG_OK) return rc;
-    pg_ctx::TokSlot &T = c->tok[slot];
-    if (off < 0 || len < 0 || (len && !dst) || off + len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_s2g_dev_text: bad range");
-    return len ? pg_copy_back(c, dst, T.tp + off, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_text(c, slot, off, len, dst, "pg_s2g_dev_text: bad range");
 }
 
 // len residues from the host to store[off ..) (a block the host route stripped; a phylip file's sequences), what stands in front kept
@@ -427,7 +411,7 @@ extern "C" int pg_s2g_dev_emit(pg_ctx *c, const int32_t *seg, const int64_t *x0,
     hipStream_t st = c->stream_up;
     int rc;
     if ((rc = D.out.ensure_roomy((size_t)out_len + 64)) != PG_OK || (rc = D.jobs.ensure_roomy(jobs.size() * sizeof(S2gJob))) != PG_OK ||
-        (rc = D.est.ensure(PGL_STATUS_WORDS)) != PG_OK || (rc = D.h_est.ensure(PGL_STATUS_WORDS)) != PG_OK)
+        (rc = D.est.status.ensure(PGL_STATUS_WORDS)) != PG_OK || (rc = D.est.h_status.ensure(PGL_STATUS_WORDS)) != PG_OK)
         return rc;
     HIPCHK(hipMemcpyAsync(D.jobs.p, jobs.data(), jobs.size() * sizeof(S2gJob), hipMemcpyHostToDevice, st));
     S2gTileArgs A;
@@ -446,16 +430,16 @@ extern "C" int pg_s2g_dev_emit(pg_ctx *c, const int32_t *seg, const int64_t *x0,
     hipLaunchKernelGGL(k_s2g_tile, dim3((unsigned)jobs.size(), (unsigned)D.n_tiles), dim3(PGS_TILE_THREADS), lds, st, A);
     HIPCHK(hipGetLastError());
     if (bgzf) {
-        pgl_preset(D.h_est.p, false);
-        D.h_est.p[PGL_ST_BYTES] = out_len;
-        HIPCHK(hipMemcpyAsync(D.est.p, D.h_est.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
-        long long *est = reinterpret_cast<long long *>(D.est.p);
+        pgl_preset(D.est.h_status.p, false);
+        D.est.h_status.p[PGL_ST_BYTES] = out_len;
+        if ((rc = pg_line_status_upload(D.est, st)) != PG_OK) return rc;
+        long long *est = reinterpret_cast<long long *>(D.est.status.p);
         if ((rc = pg_deflate_queue(c, st, c->deflate, D.out.p, est + PGL_ST_BYTES, (int64_t)D.out.cap - 64, est, est + PGL_ST_BGZF_BYTES)) != PG_OK)
             return rc;
-        HIPCHK(hipMemcpyAsync(D.h_est.p, D.est.p, PGL_STATUS_WORDS * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(D.est.h_status.p, D.est.status.p, PGL_STATUS_WORDS * 8, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(hipStreamSynchronize(st));                             // (jobs leaves scope; the rows are read next)
-    if (bgzf && bgzf_len_out) *bgzf_len_out = D.h_est.p[PGL_ST_BGZF_BYTES];
+    if (bgzf && bgzf_len_out) *bgzf_len_out = D.est.h_status.p[PGL_ST_BGZF_BYTES];
     ++D.out_ranges;
     return PG_OK;
 }
@@ -464,14 +448,12 @@ extern "C" int pg_s2g_dev_emit(pg_ctx *c, const int32_t *seg, const int64_t *x0,
 extern "C" int pg_s2g_dev_rows(pg_ctx *c, int which, uint8_t *dst, int64_t len) {
     if (!c || !c->s2g.configured || which < 0 || which > 1) return pg_fail(PG_ERR_ARG, "pg_s2g_dev_rows: bad argument");
     DevBuf<uint8_t> &B = which ? c->deflate.comp : c->s2g.out;
-    if (len < 0 || (len && !dst) || (size_t)len > B.cap) return pg_fail(PG_ERR_ARG, "pg_s2g_dev_rows: bad length");
-    return len ? pg_copy_back(c, dst, B.p, len) : PG_OK;
+    return pg_line_rows(c, B, dst, len, "pg_s2g_dev_rows: bad length");
 }
 
 extern "C" int pg_s2g_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out, int64_t *out_ranges_out) {
-    if (!c || !blocks_out || !host_blocks_out || !out_ranges_out) return pg_fail(PG_ERR_ARG, "pg_s2g_dev_stats: null argument");
-    *blocks_out = c->s2g.blocks;
-    *host_blocks_out = c->s2g.host_blocks;
-    *out_ranges_out = c->s2g.out_ranges;
-    return PG_OK;
+    if (!out_ranges_out) return pg_fail(PG_ERR_ARG, "pg_s2g_dev_stats: null argument");
+    int rc = pg_line_stats(c ? &c->s2g : nullptr, blocks_out, host_blocks_out, "pg_s2g_dev_stats");
+    if (rc == PG_OK) *out_ranges_out = c->s2g.out_ranges;
+    return rc;
 }

@@ -6,7 +6,7 @@
 //   k_seq_lines  a wavefront per line: '#' lines marked, the line's tabs ranked by ballots into LDS, the field count against the
 //                header's, a lane per output sequence checks its cell's length, the position as int64, whether the scaffold differs
 //                from the site's before
-//   scan         the kept lines' row indices (k_vcf_scan, pg_vcf_dev.hip)
+//   scan         the kept lines' row indices (k_rows_scan, pg_line_slot.hip)
 //   k_seq_rows   a thread per line: the sites' records gathered at their rows (line, position, run flag, where the line begins)
 //   k_seq_tile   the transpose: a workgroup takes PGS_TILE_LINES consecutive sites and a tile of output sequences; each of its waves
 //                reads a line in 64-byte steps, ranks its tabs, a lane per sequence puts the sequence's character into the LDS tile
@@ -20,8 +20,6 @@
 
 #include <algorithm>
 #include <cstring>
-
-void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap);
 
 namespace {
 
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(PGS_TILE_THREADS) void k_seq_tile(SeqArgs A, pg_seq
     }
 }
 
-int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->seq.configured, who, "pg_seq_dev_config"); }
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c ? &c->seq : nullptr, who, "pg_seq_dev_config"); }
 
 SeqArgs seq_args(pg_ctx *c, int slot) {
     pg_ctx::SeqDev &D = c->seq;
@@ -237,9 +235,7 @@ extern "C" int pg_seq_dev_config(pg_ctx *c, const pg_seq_cfg *cfg, const int32_t
 // A block of whole lines (the last byte a line feed, else the block is the host's) into text slot `slot`
 extern "C" int pg_seq_dev_submit(pg_ctx *c, int slot, const char *text, int64_t len) {
     int rc = check_slot(c, slot, "pg_seq_dev_submit");
-    if (rc != PG_OK) return rc;
-    if ((!text && len) || len < 0) return pg_fail(PG_ERR_ARG, "pg_seq_dev_submit: no text");
-    return pg_line_submit_text(c, slot, c->seq.s[slot], text, -1, 0, len, len > 0 && text[len - 1] == '\n');
+    return rc != PG_OK ? rc : pg_line_submit_plain(c, slot, c->seq.s[slot], text, len, "pg_seq_dev_submit");
 }
 
 // The same for a block that is still bgzipped: the members cross PCIe deflated, k_inflate writes their text behind `head` in the slot
@@ -279,7 +275,7 @@ extern "C" int pg_seq_dev_parse(pg_ctx *c, int slot) {
         for (hipEvent_t *e : {&Q.t0, &Q.t1, &Q.t2, &Q.t3})
             if (!*e) HIPCHK(hipEventCreate(e));
     }
-    HIPCHK(hipMemcpyAsync(Q.status.p, Q.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
+    if ((rc = pg_line_status_upload(Q, st)) != PG_OK) return rc;
     // the matrix's pad bytes (behind the last site of a sequence, up to the pitch) are zero whatever the slot held before
     HIPCHK(hipMemsetAsync(Q.out.p, 0, (size_t)D.cfg.n_seq * (size_t)Q.pitch, st));
     const SeqArgs A = seq_args(c, slot);
@@ -310,26 +306,19 @@ extern "C" int pg_seq_dev_collect(pg_ctx *c, int slot, int64_t *n_sites_out, int
     if (rc != PG_OK) return rc;
     if (!n_sites_out || !host_line_out) return pg_fail(PG_ERR_ARG, "pg_seq_dev_collect: null argument");
     pg_ctx::SeqDev::Slot &Q = c->seq.s[slot];
-    *n_sites_out = 0;
-    *host_line_out = -1;
-    if (n_lines_out) *n_lines_out = 0;
-    if (pitch_out) *pitch_out = 0;
     const bool empty = Q.L.state == PGL_EMPTY;
-    if ((rc = pg_line_collect_wait(c, slot, Q, "pg_seq_dev_collect")) != PG_OK || empty) return rc;
-    if (n_lines_out) *n_lines_out = Q.L.n_lines;
-    if (pitch_out) *pitch_out = Q.pitch;
-    if (Q.timed) {
-        float a = 0, b = 0;
-        HIPCHK(hipEventElapsedTime(&a, Q.t0, Q.t1));
-        HIPCHK(hipEventElapsedTime(&b, Q.t2, Q.t3));
-        c->seq.lines_ms += a;
-        c->seq.tile_ms += b;
-        Q.timed = false;
-    }
-    const PgLineResult R = pgl_decode(Q.h_status.p, false);
+    PgLineResult R;
+    rc = pg_line_collect(c, slot, c->seq, Q, false, nullptr, n_lines_out, &R, "pg_seq_dev_collect");
     *host_line_out = R.host_line;
     *n_sites_out = R.rows;
-    if (R.host_block) ++c->seq.host_blocks;
+    if (pitch_out) *pitch_out = rc == PG_OK && !empty ? Q.pitch : 0;
+    if (rc != PG_OK || empty || !Q.timed) return rc;
+    float a = 0, b = 0;
+    Q.timed = false;
+    HIPCHK(hipEventElapsedTime(&a, Q.t0, Q.t1));
+    HIPCHK(hipEventElapsedTime(&b, Q.t2, Q.t3));
+    c->seq.lines_ms += a;
+    c->seq.tile_ms += b;
     return PG_OK;
 }
 
@@ -366,10 +355,7 @@ extern "C" int pg_seq_dev_meta(pg_ctx *c, int slot, int64_t *pos_dst, uint8_t *r
 // host never had its text: BGZF)
 extern "C" int pg_seq_dev_text(pg_ctx *c, int slot, int64_t off, int64_t len, uint8_t *dst) {
     int rc = check_slot(c, slot, "pg_seq_dev_text");
-    if (rc != PG_OK) return rc;
-    pg_ctx::TokSlot &T = c->tok[slot];
-    if (off < 0 || len < 0 || (len && !dst) || off + len > T.len || (len && !T.tp)) return pg_fail(PG_ERR_ARG, "pg_seq_dev_text: bad range");
-    return len ? pg_copy_back(c, dst, T.tp + off, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_text(c, slot, off, len, dst, "pg_seq_dev_text: bad range");
 }
 
 extern "C" int pg_seq_dev_timing(pg_ctx *c, int on) {
@@ -379,9 +365,8 @@ extern "C" int pg_seq_dev_timing(pg_ctx *c, int on) {
 }
 
 extern "C" int pg_seq_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out, double *lines_ms_out, double *tile_ms_out) {
-    if (!c || !blocks_out || !host_blocks_out) return pg_fail(PG_ERR_ARG, "pg_seq_dev_stats: null argument");
-    *blocks_out = c->seq.blocks;
-    *host_blocks_out = c->seq.host_blocks;
+    int rc = pg_line_stats(c ? &c->seq : nullptr, blocks_out, host_blocks_out, "pg_seq_dev_stats");
+    if (rc != PG_OK) return rc;
     if (lines_ms_out) *lines_ms_out = c->seq.lines_ms;
     if (tile_ms_out) *tile_ms_out = c->seq.tile_ms;
     return PG_OK;

@@ -6,7 +6,8 @@
 //   k_vcf_heads      a thread per line: the nine fixed columns (token ends, site filters, POS, the allele table, site type, where GT
 //                    and the filtered fields stand in FORMAT) -> a PgvLine record; the size of the row when every allele is one base
 //   k_vcf_cells<0>   a wavefront per COMPLEX kept line (some allele longer or shorter than a base): the row's size
-//   k_vcf_scan       one block: the rows' places in the output (exclusive sums of the sizes), their total, their number
+//   scan             one block: the rows' places in the output (exclusive sums of the sizes), their total, their number (k_rows_scan,
+//                    pg_line_slot.hip)
 //   k_vcf_cells<1>   a wavefront per kept line: (1) the tabs behind FORMAT, 16 bytes per lane and step, ranked by a wave scan, their
 //                    positions into LDS; (2) a lane per selected sample: its column walked once (pgv_cell: the GT piece, the filtered
 //                    pieces as decimals, the allele look-up), its characters stored at the row's place + the cell's offset (a table
@@ -23,9 +24,6 @@
 #include <cstring>
 
 #include <unistd.h>
-
-int pg_deflate_queue(pg_ctx *c, hipStream_t st, pg_ctx::Deflate &D, const uint8_t *text_d, const long long *total_d, int64_t max_text,
-                     const long long *status_d, long long *comp_total_d);
 
 namespace {
 
@@ -233,41 +231,7 @@ __global__ __launch_bounds__(256) void k_vcf_cells(const uint8_t *__restrict__ t
     if (!RENDER && lane == 0) rlen[i] = run;
 }
 
-// the rows' places: exclusive sums of rlen over the lines (one block, every thread a stretch of lines), their total and number;
-// a total beyond the output buffer raises PG_ST_OVERFLOW
-__global__ __launch_bounds__(1024) void k_vcf_scan(const uint32_t *__restrict__ rlen, int64_t n_lines, int64_t *__restrict__ roff,
-                                                    long long *__restrict__ status, int64_t out_cap) {
-    __shared__ long long sh[1024], shn[1024];
-    const int64_t per = (n_lines + 1023) / 1024;
-    const int64_t a = std::min<int64_t>(n_lines, (int64_t)threadIdx.x * per), b = std::min<int64_t>(n_lines, a + per);
-    long long mine = 0, rows = 0;
-    for (int64_t k = a; k < b; ++k) {
-        mine += rlen[k];
-        rows += rlen[k] != 0;
-    }
-    sh[threadIdx.x] = mine;
-    shn[threadIdx.x] = rows;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const long long x = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0, y = (int)threadIdx.x >= d ? shn[threadIdx.x - d] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += x;
-        shn[threadIdx.x] += y;
-        __syncthreads();
-    }
-    long long run = sh[threadIdx.x] - mine;
-    for (int64_t k = a; k < b; ++k) {
-        roff[k] = run;
-        run += rlen[k];
-    }
-    if (threadIdx.x == 1023) {
-        status[PGL_ST_BYTES] = sh[1023];
-        status[PGL_ST_ROWS] = shn[1023];
-        if (sh[1023] > out_cap) atomicOr(reinterpret_cast<unsigned long long *>(status + PGL_ST_BITS), (unsigned long long)PG_ST_OVERFLOW);
-    }
-}
-
-int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c && c->vcf.configured, who, "pg_vcf_dev_config"); }
+int check_slot(pg_ctx *c, int slot, const char *who) { return pg_line_check_slot(c, slot, c ? &c->vcf : nullptr, who, "pg_vcf_dev_config"); }
 
 }  // namespace
 
@@ -383,11 +347,6 @@ extern "C" int pg_vcf_dev_submit_bgzf(pg_ctx *c, int slot, const uint8_t *comp, 
                                line_len_hint > 0 ? line_len_hint : 64, true, last_is_newline != 0);
 }
 
-// the rows' places of a block (k_vcf_scan), for the other per-line renderers (pg_filter_dev.hip): status [0] bits, [2] bytes, [3] rows
-void pg_rows_scan_queue(hipStream_t st, const uint32_t *rlen, int64_t n_lines, int64_t *roff, long long *status, int64_t out_cap) {
-    hipLaunchKernelGGL(k_vcf_scan, dim3(1), dim3(1024), 0, st, rlen, n_lines, roff, status, out_cap);
-}
-
 // Queues the kernels of the block in `slot` (waits for the number of its lines only).
 extern "C" int pg_vcf_dev_parse(pg_ctx *c, int slot) {
     int rc = check_slot(c, slot, "pg_vcf_dev_parse");
@@ -412,7 +371,7 @@ extern "C" int pg_vcf_dev_parse(pg_ctx *c, int slot) {
     // length again on top of the plain rows' bound, a total beyond it sends the block to the host
     V.out_cap = T.len + n_lines * (int64_t)(D.cfg.plain_cells + 64) + 4096;
     if ((rc = V.out.ensure_roomy((size_t)V.out_cap)) != PG_OK) return rc;
-    HIPCHK(hipMemcpyAsync(V.status.p, V.h_status.p, PGL_STATUS_WORDS * 8, hipMemcpyHostToDevice, st));
+    if ((rc = pg_line_status_upload(V, st)) != PG_OK) return rc;
     PgvLine *lines = reinterpret_cast<PgvLine *>(V.lines.p);
     long long *status = reinterpret_cast<long long *>(V.status.p);
     const PgvKey *prev = reinterpret_cast<const PgvKey *>(D.prevkey.p);
@@ -425,7 +384,7 @@ extern "C" int pg_vcf_dev_parse(pg_ctx *c, int slot) {
     const size_t lds = (size_t)wpb * (size_t)D.cfg.n_vcf_samples * 4;
     hipLaunchKernelGGL((k_vcf_cells<0>), grid, dim3(64 * wpb), lds, st, T.tp, T.nl.p, n_lines, D.cfg, D.sel_col.p, D.ploidy.p, D.fsel.p,
                        D.cell_off.p, lines, V.rlen.p, V.roff.p, V.out.p, status, wpb);
-    hipLaunchKernelGGL(k_vcf_scan, dim3(1), dim3(1024), 0, st, V.rlen.p, n_lines, V.roff.p, status, V.out_cap);
+    pg_rows_scan_queue(st, V.rlen.p, n_lines, V.roff.p, status, V.out_cap);
     hipLaunchKernelGGL((k_vcf_cells<1>), grid, dim3(64 * wpb), lds, st, T.tp, T.nl.p, n_lines, D.cfg, D.sel_col.p, D.ploidy.p, D.fsel.p,
                        D.cell_off.p, lines, V.rlen.p, V.roff.p, V.out.p, status, wpb);
     HIPCHK(hipGetLastError());
@@ -454,19 +413,13 @@ extern "C" int pg_vcf_dev_collect(pg_ctx *c, int slot, int64_t *out_len_out, int
     int rc = check_slot(c, slot, "pg_vcf_dev_collect");
     if (rc != PG_OK) return rc;
     if (!out_len_out || !n_rows_out || !host_line_out) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_collect: null argument");
-    pg_ctx::VcfDev::Slot &V = c->vcf.s[slot];
-    *out_len_out = *n_rows_out = 0;
-    *host_line_out = -1;
-    if (bgzf_len_out) *bgzf_len_out = 0;
-    const bool empty = V.L.state == PGL_EMPTY;
-    if ((rc = pg_line_collect_wait(c, slot, V, "pg_vcf_dev_collect")) != PG_OK || empty) return rc;
-    const PgLineResult R = pgl_decode(V.h_status.p, c->vcf.bgzf_rows);
+    PgLineResult R;
+    rc = pg_line_collect(c, slot, c->vcf, c->vcf.s[slot], c->vcf.bgzf_rows, nullptr, nullptr, &R, "pg_vcf_dev_collect");
     *host_line_out = R.host_line;
     *out_len_out = R.bytes;
     *n_rows_out = R.rows;
     if (bgzf_len_out) *bgzf_len_out = R.bgzf_bytes;
-    if (R.host_block) ++c->vcf.host_blocks;
-    return PG_OK;
+    return rc;
 }
 
 // bgzf_members != 0: the rows of every block parsed from now on are also deflated on the device (k_deflate: BGZF members of 65 280 bytes
@@ -479,34 +432,22 @@ extern "C" int pg_vcf_dev_set_output(pg_ctx *c, int bgzf_members) {
 
 extern "C" int pg_vcf_dev_rows_bgzf(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_vcf_dev_rows_bgzf");
-    if (rc != PG_OK) return rc;
-    pg_ctx::VcfDev::Slot &V = c->vcf.s[slot];
-    if (len < 0 || (len && !dst) || (size_t)len > V.df.comp.cap) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_rows_bgzf: bad length");
-    return len ? pg_copy_back(c, dst, V.df.comp.p, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_rows(c, c->vcf.s[slot].df.comp, dst, len, "pg_vcf_dev_rows_bgzf: bad length");
 }
 
 // the rows of the collected block -> dst (len = what collect reported; page-locked dst: one DMA at the link's rate)
 extern "C" int pg_vcf_dev_rows(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_vcf_dev_rows");
-    if (rc != PG_OK) return rc;
-    pg_ctx::VcfDev::Slot &V = c->vcf.s[slot];
-    if (len < 0 || (len && !dst) || (size_t)len > V.out.cap) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_rows: bad length");
-    return len ? pg_copy_back(c, dst, V.out.p, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_rows(c, c->vcf.s[slot].out, dst, len, "pg_vcf_dev_rows: bad length");
 }
 
 // the text of the collected block -> dst (a block that goes to the host parser and whose text the host never had: BGZF)
 extern "C" int pg_vcf_dev_text(pg_ctx *c, int slot, uint8_t *dst, int64_t len) {
     int rc = check_slot(c, slot, "pg_vcf_dev_text");
-    if (rc != PG_OK) return rc;
-    pg_ctx::TokSlot &T = c->tok[slot];
-    if (len < 0 || (len && !dst) || len > T.len || !T.tp) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_text: bad length");
-    return len ? pg_copy_back(c, dst, T.tp, len) : PG_OK;
+    return rc != PG_OK ? rc : pg_line_text(c, slot, 0, len, dst, "pg_vcf_dev_text: bad length");
 }
 
 // blocks parsed on the device / handed to the host so far
 extern "C" int pg_vcf_dev_stats(pg_ctx *c, int64_t *blocks_out, int64_t *host_blocks_out) {
-    if (!c || !blocks_out || !host_blocks_out) return pg_fail(PG_ERR_ARG, "pg_vcf_dev_stats: null argument");
-    *blocks_out = c->vcf.blocks;
-    *host_blocks_out = c->vcf.host_blocks;
-    return PG_OK;
+    return pg_line_stats(c ? &c->vcf : nullptr, blocks_out, host_blocks_out, "pg_vcf_dev_stats");
 }

@@ -295,7 +295,7 @@ int pg_vcf_render_rows(const char *buf, int64_t n_rows, int n_sel, const int32_t
  *   pg_vcf_dev_submit        a block of whole lines -> text slot `slot` (0 / 1): from memory, or len bytes at file_offset of fd
  *   pg_vcf_dev_submit_bgzf   the same for a block of BGZF members (table: pg_bgzf_walk; head = text the caller holds in front of them,
  *                            text_len = head + members cut behind the block's last line feed; line_len_hint = bytes of a typical line)
- *   pg_vcf_dev_parse         queues k_vcf_heads / k_vcf_cells / k_vcf_scan on the block of `slot`
+ *   pg_vcf_dev_parse         queues k_vcf_heads / k_vcf_cells / k_rows_scan on the block of `slot`
  *   pg_vcf_dev_collect       waits for them.  *host_line_out < 0: *out_len_out bytes of rows (*n_rows_out rows) are ready for
  *                            pg_vcf_dev_rows; else line *host_line_out of the block is one the device does not take (or the host
  *                            parser would answer with an error): the BLOCK goes to pg_encode_vcf (pg_vcf_dev_text brings its text back
@@ -769,7 +769,7 @@ int pg_eig_text(const pg_eig_cfg *cfg, const int32_t *sel_col, const int32_t *pr
  *                             --chromFile exceeds PG_EIG_MAX_SCAF scaffolds or PG_EIG_MAX_LABEL bytes in a label
  *   pg_eig_dev_submit / _submit_bgzf / _collect / _text / _stats   as pg_gvcf_dev_*
  *   pg_eig_dev_parse          first_site: the sites in front of the block; k_eig_lines<0> counts over all columns, decides, sizes
- *                             the .snp rows, k_eig_scan ranks and places them, k_eig_lines<1> writes both outputs; *n_lines_out the
+ *                             the .snp rows, k_rows_scan ranks and places them, k_eig_lines<1> writes both outputs; *n_lines_out the
  *                             block's lines
  *   pg_eig_dev_rows           which = 0 the .geno rows (n_rows (n_sel + 1) bytes), 1 the .snp rows */
 #define PG_EIG_MAX_SCAF (1 << 22)

@@ -1,4 +1,4 @@
-// The device route of the genoToEigenstrat.py drop-in walked on the host: what k_eig_lines and k_eig_scan
+// The device route of the genoToEigenstrat.py drop-in walked on the host: what k_eig_lines and k_rows_scan
 // (genomics_general_amd/csrc/pg_eig_dev.hip) do with a block -- the regular-spelling test, the position, the cells of ALL columns in
 // the lanes' order and their base counts summed lane by lane, the site's decision, the label's entry, the .snp row's size, the ranks
 // and places, the digits of the SELECTED columns at rank x (n_sel + 1), the .snp row's bytes at their place -- with the very functions
@@ -102,7 +102,7 @@ extern "C" int pge_emul_block(const pg_eig_cfg *cfg, const int32_t *sel_col, con
     int64_t total = 0, rows = 0;
     for (size_t i = 0; i < lines.size(); ++i) {
         if (size_line(*cfg, F, label_off, first_site + (int64_t)i, lines[i], &sites[i])) { *host_line = (int64_t)i; return 1; }
-        roff[i] = total;                                           // k_eig_scan
+        roff[i] = total;                                           // k_rows_scan
         rank[i] = rows;
         total += sites[i].rlen;
         rows += sites[i].rlen != 0;

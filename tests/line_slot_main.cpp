@@ -1,8 +1,9 @@
 // csrc/pg_line_slot.h walked as a program of its own (no GPU, no library): every state of a PgLineSlot against every event, the
 // decision that a block is the host's before any kernel runs, the status words a block starts from, and what collect makes of the
-// words that come back.  The expected values are written out here as pg_vcf_dev_*, pg_filter_dev_* and pg_seq_dev_* gave them
-// before the protocol was lifted out of those files: states 0 idle, 1 submitted, 2 queued, 3 empty; status bit 1 a line needs the
-// host, bit 2 the rows exceed their buffer.  Prints "N checks, 0 bad"; exit status 1 when a check fails.
+// words that come back, whether the rows are rendered a second time and from which words, and the range checks of the copies back.
+// The expected values are written out here as the seven routes' pg_*_dev_* entry points gave them before the protocol was lifted
+// out of their files: states 0 idle, 1 submitted, 2 queued, 3 empty; status bit 1 a line needs the host, bit 2 the rows exceed their
+// buffer.  Prints "N checks, 0 bad"; exit status 1 when a check fails.
 #include "../genomics_general_amd/csrc/pg_line_slot.h"
 
 #include <cstdio>
@@ -137,6 +138,51 @@ int main() {
         const PgLineResult r = pgl_decode(c.st, c.bgzf_rows != 0);
         check(r.host_line == c.host_line && r.bytes == c.bytes && r.rows == c.rows && r.bgzf_bytes == c.bgzf_bytes && r.host_block == c.host_block,
               "the collect decode", (int)k, c.bgzf_rows);
+    }
+
+    // ---- the second render (pg_filter_dev_collect, pg_gvcf_dev_collect, pg_eig_dev_collect, pg_ped_dev_collect before they shared it):
+    // only when the overflow bit stands alone; it starts from the same words with the bits cleared -- and, in the two routes that
+    // deflate their rows, the members' bytes
+    static const bool want_again[4] = {false, false, true, false};         // bits 0, HOST, OVERFLOW, HOST | OVERFLOW
+    for (int bits = 0; bits < 4; ++bits) {
+        const int64_t st[5] = {bits, 4, 300, 7, 90};
+        check(pgl_render_again(st) == want_again[bits], "render again", bits);
+    }
+    for (int bgzf = 0; bgzf < 2; ++bgzf) {
+        int64_t st[6] = {2, 0x7fffffffffffffffll, 300, 7, 90, -5};
+        pgl_preset_again(st, bgzf != 0);
+        check(st[0] == 0 && st[1] == 0x7fffffffffffffffll && st[2] == 300 && st[3] == 7 && st[4] == (bgzf ? 0 : 90) && st[5] == -5,
+              "the second render's preset", bgzf);
+        check(!pgl_render_again(st) && pgl_decode(st, bgzf != 0).bytes == 300 && pgl_decode(st, bgzf != 0).rows == 7, "... read by collect", bgzf);
+    }
+
+    // ---- the copies back.  pg_*_dev_text: bytes [off, off + len) of a text of `have` bytes (the routes that take no offset: off = 0) ----
+    {
+        const int64_t have = 10;
+        static const int64_t v[5] = {0, 1, have - 1, have, have + 1};
+        static const bool want_in[5][5] = {/* off 0        */ {true, true, true, true, false},       // len 0, 1, have - 1, have, have + 1
+                                           /* off 1        */ {true, true, true, false, false},
+                                           /* off have - 1 */ {true, true, false, false, false},
+                                           /* off have     */ {true, false, false, false, false},
+                                           /* off have + 1 */ {false, false, false, false, false}};
+        for (int a = 0; a < 5; ++a)
+            for (int b = 0; b < 5; ++b) check(pgl_range_ok(v[a], v[b], have, true, true) == want_in[a][b], "a text range", a, b);
+        check(!pgl_range_ok(-1, 1, have, true, true) && !pgl_range_ok(-1, 0, have, true, true), "a negative offset");
+        check(!pgl_range_ok(0, -1, have, true, true) && !pgl_range_ok(have, -1, have, true, true), "a negative length");
+        check(pgl_range_ok(0, 0, have, false, true) && pgl_range_ok(have, 0, have, false, true), "no destination, nothing to copy");
+        check(!pgl_range_ok(0, 1, have, false, true) && !pgl_range_ok(0, have, have, false, true), "no destination");
+        check(!pgl_range_ok(0, 1, have, true, false) && !pgl_range_ok(0, 1, 0, true, false), "no text in the slot");
+        check(pgl_range_ok(0, 0, 0, true, false) && pgl_range_ok(0, 0, 0, false, false), "no text in the slot, nothing to copy");
+        check(pgl_range_ok(0, 0, 0, true, true) && !pgl_range_ok(0, 1, 0, true, true), "a text of no bytes");
+    }
+    // pg_*_dev_rows / _rows_bgzf: the first len bytes of a buffer of `cap` bytes
+    {
+        const uint64_t cap = 4096;
+        check(pgl_rows_ok(0, cap, true) && pgl_rows_ok(1, cap, true) && pgl_rows_ok((int64_t)cap, cap, true), "rows inside their buffer");
+        check(!pgl_rows_ok((int64_t)cap + 1, cap, true), "rows beyond their buffer");
+        check(!pgl_rows_ok(-1, cap, true), "a negative number of row bytes");
+        check(pgl_rows_ok(0, cap, false) && !pgl_rows_ok(1, cap, false), "rows without a destination");
+        check(pgl_rows_ok(0, 0, true) && !pgl_rows_ok(1, 0, true), "a buffer never made");
     }
     printf("%d checks, %d bad\n", n_checks, n_bad);
     return n_bad ? 1 : 0;

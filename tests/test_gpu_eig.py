@@ -1,7 +1,7 @@
-"""The genoToEigenstrat.py drop-in's device route (pg_eig_dev_*: k_eig_lines, k_eig_scan) on an MI355X: every golden of the unmodified
+"""The genoToEigenstrat.py drop-in's device route (pg_eig_dev_*: k_eig_lines, k_rows_scan) on an MI355X: every golden of the unmodified
 reference the device takes, the three files byte for byte from gzip, plain and BGZF input (members inflated on the device), in one
 block and in many small ones; then device against host route on seeded files of 300 lines: column counts at the edges of the lanes'
-stride; three of 1 100 columns selected where only the others make the sites biallelic; .snp rows longer than their text; site indices
+stride; line counts at the edges of the scan's 1 024 threads; three of 1 100 columns selected where only the others make the sites biallelic; .snp rows longer than their text; site indices
 over many blocks; a scaffold change and an unlisted scaffold inside a block; a cell of ten alleles, a double tab and a '#' line that
 each hand their block to the host; --cumulativePos and a repeated header name, the host's for the whole run.  Each run is a process
 of its own under a time limit; PG_TIMING's counters show where the blocks went."""
@@ -115,6 +115,20 @@ def test_column_counts_at_the_edges_of_the_lane_stride(n_cols, tmp_path):
     rows = got["geno"].split(b"\n")[:-1]
     assert 10 < len(rows) < 300 and all(len(r) == n_cols for r in rows) and got["snp"].count(b"\n") == len(rows)
     assert int(info["device_blocks"]) >= 1 and int(info["device_host_blocks"]) == 0, info
+
+
+@pytest.mark.parametrize("n_lines", [1, 1023, 1024, 1025, 2049])
+def test_line_counts_at_the_edges_of_the_scan_threads(n_lines, tmp_path):
+    """one block whose lines k_rows_scan's 1 024 threads share out one each with threads to spare, one each exactly, and two and three
+    each with the last threads left without: kept and dropped sites mixed, so that a line's rank is not its number and a wrong rank
+    or place moves a row.  (The one line of the first case is all missing by _wide's rule for every seventh line: no site is kept,
+    and the block still is the device's)"""
+    inp = str(tmp_path / "w.geno")
+    _wide(inp, 3, n_lines, 31)
+    got, info, _ = _both(inp, ["-f", "phased"], tmp_path)
+    kept = got["geno"].count(b"\n")
+    assert (0 < kept < n_lines if n_lines > 1 else kept == 0) and got["snp"].count(b"\n") == kept, kept
+    assert int(info["device_blocks"]) == 1 and int(info["device_host_blocks"]) == 0, info
 
 
 def test_three_of_1100_columns_where_the_others_alone_make_the_sites_biallelic(tmp_path):

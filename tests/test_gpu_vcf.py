@@ -1,4 +1,4 @@
-"""VCF lines parsed on the device (csrc/pg_vcf_dev.hip: k_vcf_heads / k_vcf_cells / k_vcf_scan behind pg_vcf_dev_*) against the outputs
+"""VCF lines parsed on the device (csrc/pg_vcf_dev.hip: k_vcf_heads / k_vcf_cells / k_rows_scan behind pg_vcf_dev_*) against the outputs
 of the UNMODIFIED reference parseVCF.py (tests/golden/vcf) and against the host parser (pg_encode_vcf + pg_vcf_render_rows): byte for
 byte, plain and bgzipped input, blocks of a few lines and whole files, lines the device hands to the host, thousands of sample
 columns."""

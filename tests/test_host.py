@@ -748,15 +748,17 @@ def test_the_line_slot_protocol_walked_as_a_program_of_its_own(tmp_path):
     """tests/line_slot_main.cpp: csrc/pg_line_slot.h's states, gates, host_now, preset and collect decode under AddressSanitizer and
     UndefinedBehaviorSanitizer: every state x event pair (submit of no bytes and of some, parse, collect), collect twice, parse
     without submit, the last byte known or read on the device, host_now and the preset over n_lines in {0, 1} x no_final_newline in
-    {0, 1}, the decode for each status bit alone, both, neither, with and without BGZF rows -- against values written out from the
-    route files as they stood before the protocol was lifted out of them"""
+    {0, 1}, the decode for each status bit alone, both, neither, with and without BGZF rows; whether collect renders a second time
+    for each combination of the status bits, and the words that render starts from; the range checks of the text and row copies
+    back at the edges of what there is, with negative values, without a destination or a source -- against values written out from
+    the route files as they stood before the protocol was lifted out of them"""
     import subprocess
     exe = str(tmp_path / "line_slot_main")
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "line_slot_main.cpp"), "-o", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 0, (r.returncode, r.stdout.decode()[-2000:], r.stderr.decode()[-3000:])
-    assert r.stdout.decode().strip() == "69 checks, 0 bad"
+    assert r.stdout.decode().strip() == "114 checks, 0 bad"
 
 
 def test_the_tokenizer_table_is_what_the_host_tokenizer_reads():

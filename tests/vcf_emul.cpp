@@ -1,7 +1,7 @@
 // The device path of the parseVCF.py drop-in walked on the host: the same pgv_head / pgv_cell / pgv_cell_put the kernels of
 // genomics_general_amd/csrc/pg_vcf_dev.hip are made of (csrc/pg_vcf_core.h, compiled here by g++), configured by the same
 // pgv_make_config, with the kernels' division of the work restated serially: k_vcf_heads = the loop over lines, k_vcf_cells<0> = the
-// sizes of complex rows, k_vcf_scan = the running offset, k_vcf_cells<1> = the rows' text.  tests/test_vcf.py holds its output
+// sizes of complex rows, k_rows_scan = the running offset, k_vcf_cells<1> = the rows' text.  tests/test_vcf.py holds its output
 // against the host parser (pg_encode_vcf + pg_vcf_render_rows) on every golden and on random files.  Test infrastructure.
 #include "../genomics_general_amd/csrc/pg_vcf_cfg.h"
 

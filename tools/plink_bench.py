@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from gvcf_bench import make_text  # noqa: E402
 
-KERNELS = ("k_ped_lines", "k_ped_map", "k_ped_tile", "k_seq_lines", "k_seq_rows", "k_seq_tile", "k_vcf_scan", "k_inflate")
+KERNELS = ("k_ped_lines", "k_ped_map", "k_ped_tile", "k_seq_lines", "k_seq_rows", "k_seq_tile", "k_rows_scan", "k_inflate")
 
 
 def timed(cmd, env):

@@ -22,7 +22,7 @@ import plink_bench  # noqa: E402
 from gvcf_bench import make_text  # noqa: E402
 from plink_bench import merge_json, summary, timed  # noqa: E402
 
-plink_bench.KERNELS = ("k_s2g_lines", "k_s2g_gather", "k_s2g_heads", "k_s2g_tile", "k_seq_lines", "k_seq_rows", "k_seq_tile", "k_vcf_scan",
+plink_bench.KERNELS = ("k_s2g_lines", "k_s2g_gather", "k_s2g_heads", "k_s2g_tile", "k_seq_lines", "k_seq_rows", "k_seq_tile", "k_rows_scan",
                        "k_inflate", "k_deflate")
 
 
