@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/popgen_hip.h"
 #include "pg_nib.h"
+#include "pg_np_sum.h"
 #include "pg_pair_plan.h"     // PG_XV_PLANES, PG_GROUP, PG_XV_CAP; the routes and switches of the pack-and-pair pass
 
 #define PG_MAX_POPS 16          // populations handled by the site-statistics kernels (K3/K6 take any number)
@@ -176,28 +177,5 @@ int pg_line_rows(pg_ctx *c, const DevBuf<uint8_t> &B, uint8_t *dst, int64_t len,
 int pg_line_stats(const PgLineRoute *D, int64_t *blocks_out, int64_t *host_blocks_out, const char *who);
 
 // ---- shared device routines ---------------------------------------------------------------------------
-// float64 sum in the order NumPy's add.reduce visits a contiguous array, by one lane (k_hapstats: the reference's
-// `(clusterFreq**2).sum()`, genomics.py:1088-1091; k_paint: np.nanmean of a population's distances): fewer than 8 elements left to
-// right; up to 128 in eight strided partial sums combined as a tree, the tail added one by one; beyond that the range is halved (the
-// first half rounded down to a multiple of 8), DEPTH times at most.
-template <int DEPTH>
-__device__ double np_pairwise_sum(const double *a, int n) {
-    if (n < 8) {
-        double r = 0.0;
-        for (int i = 0; i < n; ++i) r += a[i];
-        return r;
-    }
-    if (n <= 128 || DEPTH == 0) {
-        double r[8];
-        for (int j = 0; j < 8; ++j) r[j] = a[j];
-        int i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += a[i];
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_sum<(DEPTH > 0 ? DEPTH - 1 : 0)>(a, n2) + np_pairwise_sum<(DEPTH > 0 ? DEPTH - 1 : 0)>(a + n2, n - n2);
-}
+// (np_pairwise_sum, the float64 sum in NumPy's order by one lane -- k_hapstats, k_paint --: pg_np_sum.h, which the tests also build as
+// plain host code)

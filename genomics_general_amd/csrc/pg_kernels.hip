@@ -408,7 +408,7 @@ void pg_launch_sample_het(hipStream_t st, const int32_t *Cmat, const int32_t *Dm
 //   3. f = sizes / n;  H1 = sum f^2,  H12 = H1 + 2 f0 f1,  H2 = sum_{k>=1} f_k^2  (H12 = H1, H2 = 0 for a single cluster).
 // `order[pop_start[p] .. pop_start[p+1])` = the population's slots in the reference's row order.
 // ------------------------------------------------------------------------------------------------------
-// (np_pairwise_sum, the float64 sum in NumPy's add.reduce order by one lane: pg_internal.h)
+// (np_pairwise_sum, the float64 sum in NumPy's add.reduce order by one lane: pg_np_sum.h)
 __global__ __launch_bounds__(256) void k_hapstats(const int32_t *__restrict__ Cmat, const int32_t *__restrict__ Dmat, int N,
                                                   int cN, int cshift, const int32_t *__restrict__ pop_start, int n_pops,
                                                   const int32_t *__restrict__ order, int min_pair_sites, int diag_nan,

@@ -8,7 +8,7 @@
 //        decide ranks); nan where C < minSites or C == 0.  The pair matrices carry no diagonal: C of an individual with itself is its
 //        own called count (k_hap_called), D is 0.
 //     2. lane p forms np.nanmean of population p: nan as 0, the sum in NumPy's order for a contiguous 1-d array by the one-lane routine
-//        k_hapstats uses (np_pairwise_sum, pg_internal.h), divided by the number of values that are not nan.
+//        k_hapstats uses (np_pairwise_sum, pg_np_sum.h), divided by the number of values that are not nan.
 //     3. best = np.argmin(means): the first nan if there is one, else the first minimum.
 //     4. test mode: for every other population q without a nan on either side, the doubled rank sum of the best population's values
 //        among both lists, 2 s = sum_a (1 + 2 #{v < d_a} + #{v == d_a}) (average ranks; the count of equals includes d_a), as integer
@@ -71,7 +71,8 @@ __global__ __launch_bounds__(64 * PAINT_WAVES) void k_paint(const int32_t *__res
     if (lane < n_pops) {
         const int s = ref_start[lane], n = ref_start[lane + 1] - s;
         // np.nanmean: nan as 0 (written back into the lane's own segment: a list with a nan is never ranked below), the sum in
-        // NumPy's order (np_pairwise_sum, pg_internal.h: at most 2048 values, five levels of halves), over the values that are not nan
+        // NumPy's order (np_pairwise_sum, pg_np_sum.h: at most PAINT_MAX_REFS = 2048 values, which take up to five levels of halves --
+        // 2047 does, 2048 takes four --; the depth of 6 holds the order up to 121 << 6 values), over the values that are not nan
         int cnt = 0;
         for (int t = 0; t < n; ++t) {
             if (q[s + t] == q[s + t]) ++cnt;

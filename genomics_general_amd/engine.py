@@ -829,22 +829,24 @@ class WindowBatch:
         the reference's order, duplicates kept.  delta_threshold None: the rank-sum test against p_threshold (the device compares
         integer rank sums with paint_crit's table); else the two lowest means must lie delta_threshold apart, and the cells with a
         nan among their means come back with those means and are finished here with Python's sorted(), as the reference does it
-        (self.paint_host_cells: which cells those were).  Every window is decided, whatever its number of sites: a driver leaves
-        out the windows below its minSites."""
+        (self.paint_host_cells: which cells those were; self.paint_host_count: how many entries the device's list had -- a cell
+        listed twice would show only here).  What the library refuses -- more populations or reference individuals than k_paint
+        takes, a population without individuals, the delta mode with one population -- comes back as its PopgenError.  Every
+        window is decided, whatever its number of sites: a driver leaves out the windows below its minSites."""
         lay = self.lay
         assert lay.n_hap == lay.n_samp, "paint: every sample must be haploid (distPaint.py reads its file that way)"
         n_ind = lay.n_hap
         lists = [np.asarray(r, dtype=np.int64).ravel() for r in ref_lists]
-        assert len(lists) >= 1 and all(len(r) >= 1 for r in lists), "paint: every reference population needs an individual"
-        assert all(r.min() >= 0 and r.max() < n_ind for r in lists), "paint: reference index outside the individuals"
+        assert len(lists) >= 1, "paint: no reference population"
+        assert all(len(r) == 0 or (r.min() >= 0 and r.max() < n_ind) for r in lists), "paint: reference index outside the individuals"
         delta = delta_threshold is not None
-        assert not delta or len(lists) >= 2, "paint: the delta mode needs two populations"
         order = np.ascontiguousarray(lay.ref_order, dtype=np.int32)
         start = np.zeros(len(lists) + 1, dtype=np.int32)
         start[1:] = np.cumsum([len(r) for r in lists])
         slots = np.ascontiguousarray(order[np.concatenate(lists)], dtype=np.int32)
         out = np.zeros((self.n, n_ind), dtype=np.int32)
         self.paint_host_cells = np.zeros((self.n, n_ind), dtype=bool)
+        self.paint_host_count = 0
         if self.n == 0:
             return out
         crit = None if delta else paint_crit([len(r) for r in lists], p_threshold)
@@ -855,7 +857,7 @@ class WindowBatch:
         check(self.e._L.pg_paint(self.e._h, self.lo, self.hi, self.n, n_ind, order, len(lists), start, slots, int(minSites), 1 if delta else 0,
                                  C.c_void_p(crit.ctypes.data) if crit is not None else None, float(delta_threshold) if delta else 0.0,
                                  int(noresult), out, C.byref(n_flag), C.c_void_p(fcell.ctypes.data), C.c_void_p(fmean.ctypes.data)))
-        nf = int(n_flag.value)
+        nf = self.paint_host_count = int(n_flag.value)
         if nf:
             # every such cell has a nan mean: np.argmin is its first nan; sorted() compares floats as it compares np.float64.  One
             # sorted() of a short list of Python floats per cell (about half a microsecond each: a batch with most of 10^6 cells
@@ -929,6 +931,8 @@ def paint_crit(sizes, p_threshold):
             if b == q:
                 continue
             n1, n2 = int(sizes[b]), int(sizes[q])
+            if n1 == 0 or n2 == 0:                                                  # (an empty population: the library refuses the call)
+                continue
             if (n1, n2) not in known:
                 lo, hi = n1 * (n1 + 1), n1 * (n1 + 2 * n2 + 1)
                 if not ranksum_less_p(n1, n2, lo) <= p_threshold:               # (a nan threshold assigns everything: nan > t is false)

@@ -570,7 +570,8 @@ def test_rccl_communicator_single_rank_roundtrip(tmp_path, monkeypatch):
     (False, False, 0, 2500), (True, False, 0, 2500), (False, True, 0.002, 6000), (True, True, 0.01, 20000)])
 def test_sample_het_and_h12_finished_on_the_device_match_the_oracle(after_popdist, after_indpair, max_dist, var_thr):
     """pg_sample_het / pg_hapstats (genomics.py:918-929, 1079-1098, 1239-1261) on the matrix the reference's worker has cached
-    at that point: plain, masked by a preceding groupDistStats(minSites), or with the nan diagonal indPairDists leaves"""
+    at that point: plain, masked by a preceding groupDistStats(minSites), or with the nan diagonal indPairDists leaves; bit for bit
+    (the quotients are IEEE divisions, the sums run in NumPy's order: tests/test_gpu_finishers.py has the larger populations)"""
     e, lay, codes, names = G.make_engine(17, 3, 2600, seed=71, var_thr=var_thr, miss_thr=2500, extra_nopop=2)
     wins = [(0, 300), (300, 340), (340, 2600), (7, 8), (1000, 1064)]
     ms = 25
@@ -593,11 +594,11 @@ def test_sample_het_and_h12_finished_on_the_device_match_the_oracle(after_popdis
             np.fill_diagonal(dm, np.nan)
         want_het = orc.sample_het(aln, dm, Co)
         for nm in names:
-            assert G.close(het[nm][k], want_het["het_" + nm]), (nm, k, het[nm][k], want_het["het_" + nm])
+            assert G.same(het[nm][k], want_het["het_" + nm]), (nm, k, het[nm][k], want_het["het_" + nm])
         want_h = orc.h12_stats(aln, dm, max_dist)
         for p in lay.sampleData.popNames:
             for st in ("H1_", "H12_", "H2_"):
-                assert G.close(h[st + p][k], want_h[st + p]), (st + p, k, h[st + p][k], want_h[st + p])
+                assert G.same(h[st + p][k], want_h[st + p]), (st + p, k, h[st + p][k], want_h[st + p])
             sizes_seen.add(round(float(want_h["H1_" + p]), 6))
     assert len(sizes_seen) >= 2                     # the cases are not all "every haplotype its own cluster"
     e.close()

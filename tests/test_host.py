@@ -678,6 +678,55 @@ def test_the_pair_pass_plan_walked_as_a_program_of_its_own(tmp_path):
     assert n_cases == 732 and r.stdout.decode().strip() == "%d cases, 0 bad" % n_cases
 
 
+def test_the_one_lane_numpy_sum_adds_up_like_numpy_as_a_program_of_its_own(tmp_path):
+    """tests/np_sum_main.cpp: csrc/pg_np_sum.h's np_pairwise_sum -- what k_hapstats sums f^2 with (depth 9, and the view behind the
+    first cluster for H2) and k_paint a population's distances (depth 6) -- as host code under AddressSanitizer and
+    UndefinedBehaviorSanitizer, against np.sum to the last bit: every length 0 .. 300 and the lengths around 512, 1024, 2048, 4096 and
+    8192 (above 2048, k_paint's limit, for depth 9 only).  The values are signed with magnitudes spread log-uniformly over 1e-8 .. 1e8,
+    so that the order of the additions shows: a left-to-right sum of the same values must differ from np.sum at three quarters of
+    the lengths from 16 on (it does at about 85 %)"""
+    import struct
+    import subprocess
+    exe = str(tmp_path / "np_sum_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "np_sum_main.cpp"),
+                           "-o", exe])
+    rng = np.random.default_rng(20261)
+    lengths = list(range(301)) + [n + d for n in (512, 1024, 2048, 4096, 8192) for d in (-1, 0, 1)]
+    arrays = [rng.choice([-1.0, 1.0], size=n) * 10.0 ** rng.uniform(-8.0, 8.0, size=n) for n in lengths]
+    src, dst = str(tmp_path / "arrays.bin"), str(tmp_path / "sums.txt")
+    with open(src, "wb") as f:
+        f.write(struct.pack("=q", len(arrays)))
+        for a in arrays:
+            f.write(struct.pack("=q", len(a)) + np.ascontiguousarray(a, dtype=np.float64).tobytes())
+    r = subprocess.run([exe, src, dst], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0, (r.returncode, r.stdout.decode()[-2000:], r.stderr.decode()[-3000:])
+    assert r.stdout.decode().strip() == "%d arrays" % len(arrays)
+    with open(dst) as f:
+        got = [[int(x, 16) for x in line.split()] for line in f]
+    assert len(got) == len(arrays)
+
+    def bits(v):
+        return int(np.float64(v).view(np.uint64))
+
+    differ = counted = 0
+    for a, (s6, s9, tail) in zip(arrays, got):
+        n = len(a)
+        want = np.sum(a) if n else np.float64(0.0)
+        assert s9 == bits(want), (n, "depth 9")
+        if n <= 2048:
+            assert s6 == bits(want), (n, "depth 6")
+        assert tail == bits(a[1:].sum() if n > 1 else 0.0), (n, "the view behind the first value")
+        if n >= 16:
+            counted += 1
+            left = 0.0
+            for x in a.tolist():
+                left += x
+            differ += bits(left) != bits(want)
+    print("left-to-right differs from np.sum at %d of %d lengths >= 16" % (differ, counted))
+    assert counted == 300 and 4 * differ >= 3 * counted, (differ, counted)
+
+
 # ---- the device tokenizer's case table (tests/tok_cases.py) and its route plan (csrc/pg_tok_plan.h), without a GPU ----------------------
 import functools  # noqa: E402
 
