@@ -409,8 +409,20 @@ def site_pop_counts(aln, members):
     return cnt, cnt.sum(axis=1)
 
 
-def abbababa(aln, P1, P2, P3, P4, min_data):
-    """genomics.py:1647-1695 ABBABABA(polarize=True) with f4/D/fd/fdm/ABBA/BABA (1409-1475,1565-1569)."""
+def _window_sums(ratios, plain):
+    """{statistic: (A, sum|a_i|, B, sum|b_i|, n)} for the ratios A / B of two window sums, (A, sum|a_i|, None, None, n) for a
+    plain sum: what a test needs to bound the difference between two orders of adding the same per-site terms up"""
+    out = {}
+    for key, (a, b) in ratios.items():
+        out[key] = (a.sum(), np.abs(a).sum(), b.sum(), np.abs(b).sum(), len(a))
+    for key, a in plain.items():
+        out[key] = (a.sum(), np.abs(a).sum(), None, None, len(a))
+    return out
+
+
+def abbababa(aln, P1, P2, P3, P4, min_data, with_sums=False):
+    """genomics.py:1647-1695 ABBABABA(polarize=True) with f4/D/fd/fdm/ABBA/BABA (1409-1475,1565-1569).
+    with_sums: (statistics, _window_sums of every statistic; empty for a window without a good site)."""
     g = np.array(aln.groups, dtype=object)
     rows = [np.where(g == p)[0] for p in (P1, P2, P3, P4)]
     cnts, ns = zip(*[site_pop_counts(aln, r) for r in rows])
@@ -422,7 +434,8 @@ def abbababa(aln, P1, P2, P3, P4, min_data):
     good = np.where(biallelic & enough)[0]
     if len(good) < 1:
         # :1693-1695 zips SIX names with SEVEN values ([nan]*6 + [0]): the 0 is dropped and sitesUsed is nan
-        return dict(D=np.nan, fd=np.nan, fdM=np.nan, ABBA=np.nan, BABA=np.nan, sitesUsed=np.nan)
+        out = dict(D=np.nan, fd=np.nan, fdM=np.nan, ABBA=np.nan, BABA=np.nan, sitesUsed=np.nan)
+        return (out, {}) if with_sums else out
     with np.errstate(divide="ignore", invalid="ignore"):
         freqs = [1. * cnts[k][good] / ns[k][good][:, None] for k in range(4)]
         allf = 1. * tot[good] / (ns[0] + ns[1] + ns[2] + ns[3])[good][:, None]
@@ -443,7 +456,14 @@ def abbababa(aln, P1, P2, P3, P4, min_data):
         pdm2 = p3 * (y & b) + p2 * (~(y & b))
         pdm3 = -p3 * (x & a) + p3 * (y & b) - p1 * (x & ~a) + p2 * (y & ~b)
         fdm = f4(p1, p2, p3, p4).sum() * 1. / f4(pdm1, pdm2, pdm3, p4).sum()
-    return dict(D=Dv, fd=fdv, fdM=fdm, ABBA=abba_t.sum(), BABA=baba_t.sum(), sitesUsed=len(ai[0]))
+    out = dict(D=Dv, fd=fdv, fdM=fdm, ABBA=abba_t.sum(), BABA=baba_t.sum(), sitesUsed=len(ai[0]))
+    if not with_sums:
+        return out
+    with np.errstate(divide="ignore", invalid="ignore"):
+        num_t = f4(p1, p2, p3, p4)
+        sums = _window_sums({"D": (num_t, abba_t + baba_t), "fd": (num_t, f4(p1, pd, pd, p4)), "fdM": (num_t, f4(pdm1, pdm2, pdm3, p4))},
+                            {"ABBA": abba_t, "BABA": baba_t})
+    return out, sums
 
 
 FOURPOP_STATS = ["ABBA", "BABA", "ABAA", "BAAA", "D", "fd", "fd'", "fdm", "fdm'", "fdh", "fdh2", "fh"]   # fourPopWindows.py:241
@@ -454,8 +474,9 @@ FOURPOP_STATS = ["ABBA", "BABA", "ABAA", "BAAA", "D", "fd", "fd'", "fdm", "fdm'"
 MINOR_TIE = {(0, 1): 1, (0, 2): 0, (0, 3): 0, (1, 2): 1, (1, 3): 1, (2, 3): 2}
 
 
-def four_pop(aln, P1, P2, P3, P4, min_data, polarize=False, fixed=False):
-    """genomics.py:1585-1643 fourPop with the per-site terms of genomics.py:1409-1563."""
+def four_pop(aln, P1, P2, P3, P4, min_data, polarize=False, fixed=False, with_sums=False):
+    """genomics.py:1585-1643 fourPop with the per-site terms of genomics.py:1409-1563.
+    with_sums: (statistics, _window_sums of every statistic; empty for a window without a good site)."""
     g = np.array(aln.groups, dtype=object)
     rows = [np.where(g == p)[0] for p in (P1, P2, P3, P4)]
     cnts, ns = zip(*[site_pop_counts(aln, r) for r in rows])
@@ -468,7 +489,7 @@ def four_pop(aln, P1, P2, P3, P4, min_data, polarize=False, fixed=False):
     if len(good) < 1:
         out = {k: np.nan for k in FOURPOP_STATS}
         out["sitesUsed"] = 0
-        return out
+        return (out, {}) if with_sums else out
     with np.errstate(divide="ignore", invalid="ignore"):
         freqs = [1. * cnts[k][good] / ns[k][good][:, None] for k in range(4)]
     totg = tot[good]
@@ -516,7 +537,17 @@ def four_pop(aln, P1, P2, P3, P4, min_data, polarize=False, fixed=False):
             "ABAA": ((1 - p1) * p2 * (1 - p3) * (1 - p4)).sum(), "BAAA": (p1 * (1 - p2) * (1 - p3) * (1 - p4)).sum(),
             "sitesUsed": len(ai[0]),
         }
-    return out
+        if not with_sums:
+            return out
+        num_t, numc_t = f4(p1, p2, p3, p4), f4c(p1, p2, p3, p4)
+        zero = np.zeros(0)
+        sums = _window_sums(
+            {"D": (num_t, abba_t + baba_t), "fd": (num_t, f4(p1, pd, pd, p4)), "fd'": (numc_t, f4c(p1, pd, pd, p4)),
+             "fdm": (num_t, f4(pdm1, pdm2, pdm3, p4)), "fdm'": (numc_t, f4c(pdm1, pdm2, pdm3, p4)),
+             "fdh": (numc_t, np.amax(h4, axis=0) if len(p1) else zero), "fdh2": (numc_t, np.amax(h8, axis=0) if len(p1) else zero),
+             "fh": (numc_t, (t1 * (t1 > t2) + t2 * (t2 >= t1)) ** 2)},
+            {"ABBA": abba_t, "BABA": baba_t, "ABAA": (1 - p1) * p2 * (1 - p3) * (1 - p4), "BAAA": p1 * (1 - p2) * (1 - p3) * (1 - p4)})
+    return out, sums
 
 
 def tajima_d(n, S, theta_pi):

@@ -264,9 +264,9 @@ def test_ind_pair_dists_with_and_without_popdist_mask():
 
 @pytest.mark.parametrize("n_dip,min_data,miss", [(16, 0.01, 5000), (16, 0.5, 20000), (16, 0.9, 9000), (16, 0.0, 50000),
                                                  (16, 1.0, 50000),      # no window has a good site: sitesUsed is nan
-                                                 (150, 0.3, 9000),      # 304-byte rows: two screening passes
-                                                 (300, 0.3, 9000),      # 608-byte rows: three of four
-                                                 (600, 0.3, 9000)])     # 1200-byte rows: quad-layout screening
+                                                 (150, 0.3, 9000),      # 300 slots: two screening passes
+                                                 (300, 0.3, 9000),      # 600 slots: three of four
+                                                 (600, 0.3, 9000)])     # 1200 slots: quad-layout screening
 def test_abbababa_sums(n_dip, min_data, miss):
     e, lay, codes, _ = G.make_engine(n_dip, 4, 6000, seed=44, var_thr=45000, miss_thr=miss)
     e.set_sum_order(1)          # NumPy's order for every window: these tests hold the NumPy-order kernels against the oracle with ==
@@ -330,8 +330,8 @@ def test_fourpop_sums(mode, n_dip, min_data, miss):
 
 
 @pytest.mark.parametrize("n_dip,n_pops,miss", [(10, 2, 400), (24, 6, 150),      # six populations: lanes own pops q and q+4
-                                                (150, 3, 20), (300, 3, 10),      # 304- and 608-byte rows
-                                                (600, 2, 5)])                    # 1200-byte rows: thread-per-site kernel
+                                                (150, 3, 20), (300, 3, 10),      # 300 and 600 slots
+                                                (600, 2, 5)])                    # 1200 slots: thread-per-site kernel
 def test_group_freq_stats_exact_integers(n_dip, n_pops, miss):
     e, lay, codes, _ = G.make_engine(n_dip, n_pops, 5000, seed=55, miss_thr=miss)
     wins = [(0, 2500), (2500, 5000), (17, 18), (31, 4097), (1000, 1000), (4990, 5000)]
