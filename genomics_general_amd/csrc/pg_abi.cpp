@@ -427,6 +427,8 @@ extern "C" int pg_set_samples(pg_ctx *c, int n_hap, const int32_t *hap_pop, cons
     std::vector<PgTask2> tasks2 = pg_make_tasks_circ(n_hap, 16);       // k_pairD: 16-row circulant tasks
     c->n_tasks2 = (int)tasks2.size();
     c->all_diploid = (n_hap % 2 == 0);
+    c->max_ploidy = 0;
+    for (size_t k = 0; k + 1 < sstart.size(); ++k) c->max_ploidy = std::max(c->max_ploidy, (int)(sstart[k + 1] - sstart[k]));
     for (size_t k = 0; k + 1 < sstart.size() && c->all_diploid; ++k)
         if (sstart[k + 1] - sstart[k] != 2) c->all_diploid = false;
     // the fast forms of k_popdist_fin (<1>, <2>) walk a population individual by individual (8-byte loads at its even slots): they
@@ -1344,12 +1346,39 @@ extern "C" int pg_np_tree(int n, int32_t *out, int64_t cap, int64_t *len) {
 
 #define PG_NP_MAX_LEAVES 1024      // LDS of a block: 2 * 1024 + 8 * 128 doubles + the tree's tables (3 * 1024 ints) + row maps: 40 KB
 
+// a layout with a block past that: the blob of a full 8192-value piece (at offset 0) and of every block's last piece, for
+// k_popdist_np_big (np_state 2: NumPy's order only where pg_set_sum_order(1) asks for it in every window)
+static int np_prepare_pieces(pg_ctx *c, const std::vector<int> &lens) {
+    std::vector<int32_t> all = np_tree(8192), task_tree;
+    std::vector<std::pair<int, int>> known;                            // (values of the last piece, offset)
+    for (int n : lens) {
+        const int m = n % 8192;
+        int off = m == 0 ? 0 : -1;
+        for (auto &kv : known) if (kv.first == m) off = kv.second;
+        if (off < 0) {
+            std::vector<int32_t> b = np_tree(m);
+            if (b[0] > 128 || b.size() - 3 > 3 * 128 + 64) { c->np_state = -1; return PG_OK; }      // (cannot happen: a run of a halved piece has >= 64 values)
+            off = (int)all.size();
+            all.insert(all.end(), b.begin(), b.end());
+            known.push_back(std::make_pair(m, off));
+        }
+        task_tree.push_back(off);
+    }
+    int rc;
+    if ((rc = c->np_trees.upload(all.data(), all.size(), c->stream)) != PG_OK) return rc;
+    if ((rc = c->np_task_tree.upload(task_tree.data(), task_tree.size(), c->stream)) != PG_OK) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->np_state = 2;
+    return PG_OK;
+}
+
 // the trees of this context's blocks: (x, x), and (x, y) / (x + y, x + y) for every pair: their lengths do not depend on the orientation
 static int np_prepare(pg_ctx *c) {
     if (c->np_state != 0) return PG_OK;
     const int P = c->n_pops;
     std::vector<int> lens;
     int side = 2;
+    bool fits = true;
     for (int p = 0; p < P; ++p) {
         const int n = c->h_pop_start[p + 1] - c->h_pop_start[p];
         if (n > 4096) { c->np_state = -1; return PG_OK; }
@@ -1359,12 +1388,13 @@ static int np_prepare(pg_ctx *c) {
     for (int x = 0; x < P; ++x)
         for (int y = x + 1; y < P; ++y) {
             const int64_t nx = c->h_pop_start[x + 1] - c->h_pop_start[x], ny = c->h_pop_start[y + 1] - c->h_pop_start[y];
-            if ((nx + ny) * (nx + ny) > (int64_t)PG_NP_MAX_LEAVES * 128) { c->np_state = -1; return PG_OK; }
+            if ((nx + ny) * (nx + ny) > (int64_t)PG_NP_MAX_LEAVES * 128) fits = false;
             lens.push_back((int)(nx * ny));
             lens.push_back((int)((nx + ny) * (nx + ny)));
             side = std::max(side, (int)(2 * (nx + ny)));
         }
-    for (int n : lens) if ((int64_t)n > (int64_t)PG_NP_MAX_LEAVES * 128) { c->np_state = -1; return PG_OK; }
+    for (int n : lens) if ((int64_t)n > (int64_t)PG_NP_MAX_LEAVES * 128) fits = false;
+    if (!fits) return np_prepare_pieces(c, lens);
     std::vector<int32_t> all, task_tree;
     std::vector<std::pair<int, int>> known;                            // (n, offset)
     int max_leaves = 1;
@@ -1373,7 +1403,7 @@ static int np_prepare(pg_ctx *c) {
         for (auto &kv : known) if (kv.first == n) off = kv.second;
         if (off < 0) {
             std::vector<int32_t> b = np_tree(n);
-            if (b[0] > PG_NP_MAX_LEAVES) { c->np_state = -1; return PG_OK; }
+            if (b[0] > PG_NP_MAX_LEAVES) return np_prepare_pieces(c, lens);
             max_leaves = std::max(max_leaves, (int)b[0]);
             off = (int)all.size();
             all.insert(all.end(), b.begin(), b.end());
@@ -1407,7 +1437,9 @@ extern "C" int pg_popdist_stats(pg_ctx *c, const int64_t *lo, const int64_t *hi,
     // tree; 20 times less work: every quotient is formed once instead of 2 .. 6 times), equal within 1e-15 -- a printed difference
     // would need a mean within 1e-16 of a tie.  The choice is made window by window (a window's numbers do not depend on what it is
     // batched with).  PG_POPDIST_TREE=1 / 0 forces one or the other.
-    const long long np_upto = c->np_state != 1 ? -1 : np_sites_limit(c, "PG_POPDIST_TREE");
+    // (a layout past k_popdist_np's LDS, np_state 2: the fixed trees, unless NumPy's order is asked for in every window)
+    long long np_upto = c->np_state < 1 ? -1 : np_sites_limit(c, "PG_POPDIST_TREE");
+    if (c->np_state == 2 && np_upto != (long long)INT64_MAX) np_upto = -1;
     const int P = c->n_pops, npairs = P * (P + 1) / 2, ncols = P + (do_pairs ? P * (P - 1) : 0);
     if ((rc = c->res_f64.ensure((size_t)n_win * P * P)) != PG_OK) return rc;           // k_popdist_np: P^2 sums a window
     if ((rc = c->res_i64.ensure((size_t)n_win * P * P)) != PG_OK) return rc;
@@ -1422,7 +1454,11 @@ extern "C" int pg_popdist_stats(pg_ctx *c, const int64_t *lo, const int64_t *hi,
         hipEvent_t e0, e1;
         int r = pg_time_begin(c, PG_K_POPDIST_FIN, &e0, &e1);
         if (r != PG_OK) return r;
-        if (any_short)
+        if (any_short && c->np_state == 2)
+            pg_launch_popdist_np_big(c->stream, c->Cmat.p, c->Dmat.p, c->n_hap, c->cN, c->cshift, nb, c->pop_start.p, P, c->ref_row.p, c->pop_rank.p,
+                                     c->np_task_tree.p, c->np_trees.p, 0, min_pair_sites, min_data, do_pairs, c->res_f64.p + (size_t)w0 * P * P,
+                                     c->res_i64.p + (size_t)w0 * P * P, c->stats.p + (size_t)w0 * ncols, c->cur_win_lo, c->cur_win_hi, np_upto);
+        else if (any_short)
             pg_launch_popdist_np(c->stream, c->Cmat.p, c->Dmat.p, c->n_hap, c->cN, c->cshift, nb, c->pop_start.p, P, c->ref_row.p,
                                  c->pop_rank.p, c->np_task_tree.p, c->np_trees.p, c->np_max_leaves, c->np_max_side, min_pair_sites, min_data, do_pairs,
                                  c->res_f64.p + (size_t)w0 * P * P, c->res_i64.p + (size_t)w0 * P * P, c->stats.p + (size_t)w0 * ncols,
@@ -1490,7 +1526,7 @@ static int indpair_run(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_wi
             hipEvent_t e0, e1;
             if ((r = pg_time_begin(c, PG_K_INDPAIR_FIN, &e0, &e1)) != PG_OK) return r;
             pg_launch_indpair_fin(c->stream, c->Cmat.p, c->Dmat.p, c->n_hap, c->cN, c->cshift, nb, c->samp_start.p, c->samp_rank.p, c->n_samp,
-                                  min_pair_sites, c->res_alt[f].p, nullptr, mean_mode);
+                                  min_pair_sites, c->res_alt[f].p, nullptr, mean_mode, c->max_ploidy);
             if ((r = pg_time_end(c, PG_K_INDPAIR_FIN, e0, e1, 1)) != PG_OK) return r;
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(c->res_fin[f], c->stream));
@@ -1515,7 +1551,7 @@ static int indpair_run(pg_ctx *c, const int64_t *lo, const int64_t *hi, int n_wi
         hipEvent_t e0, e1;
         if ((r = pg_time_begin(c, PG_K_INDPAIR_FIN, &e0, &e1)) != PG_OK) return r;
         pg_launch_indpair_fin(c->stream, c->Cmat.p, c->Dmat.p, c->n_hap, c->cN, c->cshift, nb, c->samp_start.p, c->samp_rank.p, c->n_samp, min_pair_sites,
-                              c->res_f64.p, c->res_i64.p, mean_mode);
+                              c->res_f64.p, c->res_i64.p, mean_mode, c->max_ploidy);
         if ((r = pg_time_end(c, PG_K_INDPAIR_FIN, e0, e1, 1)) != PG_OK) return r;
         HIPCHK(hipGetLastError());
         // (the table can be tens of megabytes -- 40 MB per distMat pass over 1000 diploids --: PCIe time, timed as its own family)
@@ -1561,7 +1597,7 @@ extern "C" int pg_indpairdist_mean_from_counts(pg_ctx *c, const int32_t *D, cons
         HIPCHK(hipMemcpyAsync(c->Dmat.p, D + (size_t)w0 * NN, (size_t)nb * NN * 4, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->Cmat.p, C + (size_t)w0 * NN, (size_t)nb * NN * 4, hipMemcpyHostToDevice, c->stream));
         pg_launch_indpair_fin(c->stream, c->Cmat.p, c->Dmat.p, c->n_hap, c->n_hap, 0, nb, c->samp_start.p, c->samp_rank.p, c->n_samp, min_pair_sites,
-                              c->res_f64.p, nullptr, diag_counts_zeros ? 2 : 1);
+                              c->res_f64.p, nullptr, diag_counts_zeros ? 2 : 1, c->max_ploidy);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(d_out + (size_t)w0 * npairs, c->res_f64.p, (size_t)nb * npairs * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));

@@ -341,8 +341,10 @@ struct pg_ctx {
     // the population names (pg_set_reference_order; identity until set), the pairwise-summation trees of the block lengths
     DevBuf<int32_t> ref_row, pop_rank, np_trees, np_task_tree;
     DevBuf<int32_t> samp_rank;     // k_indpair_fin: which individual of a pair supplies the rows of its haplotype block (pg_set_sample_rank)
-    int np_state = 0;              // 0: not built for the current samples; 1: usable; -1: a block has too many runs (old finisher)
+    int np_state = 0;              // 0: not built for the current samples; 1: usable; 2: a block has too many runs for k_popdist_np's LDS (the
+                                   // fixed trees; k_popdist_np_big where pg_set_sum_order(1) asks for NumPy's order); -1: a population past 4096
     int np_max_leaves = 0, np_max_side = 0;
+    int max_ploidy = 0;            // the most haplotypes of an individual (pg_set_samples): from 3 on k_indpair_fin meets blocks of 8 values and more
     int sum_order = 0;             // pg_set_sum_order: 0 = NumPy's order up to PG_NP_MAX_SITES sites a window, 1 = for every window, 2 = for none
     const int64_t *cur_win_lo = nullptr, *cur_win_hi = nullptr;   // pairwise_batches: the staged windows of the sub-batch being consumed
     // how the matrices of the last batch are laid out (set by pairwise_batches)

@@ -50,9 +50,17 @@ void pg_launch_popdist_np(hipStream_t st, const int32_t *Cmat, const int32_t *Dm
                           double min_data, int do_pairs, double *sums, int64_t *cnts, double *out, const int64_t *win_lo,
                           const int64_t *win_hi, long long max_sites);
 
+// the same with blocks of any length, a piece of 8192 values at a time (k_popdist_np_big): trees = the blob of a full piece at full_tree
+// and of every task's last piece at task_tree[task]
+void pg_launch_popdist_np_big(hipStream_t st, const int32_t *Cmat, const int32_t *Dmat, int N, int cN, int cshift, int n_win,
+                              const int32_t *pop_start, int n_pops, const int32_t *ref_row, const int32_t *pop_rank,
+                              const int32_t *task_tree, const int32_t *trees, int full_tree, int min_pair_sites, double min_data,
+                              int do_pairs, double *sums, int64_t *cnts, double *out, const int64_t *win_lo, const int64_t *win_hi,
+                              long long max_sites);
+
 void pg_launch_indpair_fin(hipStream_t st, const int32_t *Cmat, const int32_t *Dmat, int N, int cN, int cshift, int n_win,
                            const int32_t *samp_start, const int32_t *samp_rank, int n_samp, int min_pair_sites, double *sum_out,
-                           int64_t *cnt_out, int mean_mode);
+                           int64_t *cnt_out, int mean_mode, int max_ploidy);     // max_ploidy: the most haplotypes of an individual
 
 
 void pg_launch_abba(hipStream_t st, const int8_t *gt, int RS, const int64_t *win_lo, const int64_t *win_hi,

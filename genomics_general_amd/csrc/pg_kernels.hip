@@ -790,6 +790,126 @@ __global__ __launch_bounds__(256) void k_popdist_np(const int32_t *__restrict__ 
     (void)n;
 }
 
+// k_popdist_np for blocks of any length (pg_set_sum_order(1) on a layout whose trees do not fit k_popdist_np's LDS): np.add.reduce adds
+// the sums of the 8192-value pieces of the flattened block one after the other, so a piece at a time is walked: its runs and inner nodes
+// (at most 128 runs: a run of a halved piece has 64 values or more) in LDS, the pieces' sums chained by thread 0.  trees: the blob of
+// a full piece at full_tree, the blob of a task's last piece (n % 8192 values) at task_tree[task].  Same tasks, same outputs; the rows'
+// slots are read from ref_row directly.
+#define PG_NP_PIECE 8192
+#define PG_NP_PIECE_LEAVES 128
+__global__ __launch_bounds__(256) void k_popdist_np_big(const int32_t *__restrict__ Cmat, const int32_t *__restrict__ Dmat, int N, int cN,
+                                                        int cshift, const int32_t *__restrict__ pop_start, int n_pops,
+                                                        const int32_t *__restrict__ ref_row, const int32_t *__restrict__ pop_rank,
+                                                        const int32_t *__restrict__ task_tree, const int32_t *__restrict__ trees, int full_tree,
+                                                        int min_pair_sites, double *__restrict__ sum_out, int64_t *__restrict__ cnt_out,
+                                                        const int64_t *__restrict__ win_lo, const int64_t *__restrict__ win_hi,
+                                                        long long max_sites) {
+    __shared__ double slots[2 * PG_NP_PIECE_LEAVES];
+    __shared__ double q[PG_NP_STAGE_LEAVES * 128];
+    __shared__ int32_t tree_s[3 * PG_NP_PIECE_LEAVES + 64];
+    __shared__ unsigned long long shc[4];
+    if (win_hi[blockIdx.y] - win_lo[blockIdx.y] > max_sites) return;
+    const int task = blockIdx.x, win = blockIdx.y, tid = threadIdx.x;
+    const int n_tasks = gridDim.x;
+    int pa, pb, kind;                                        // as in k_popdist_np
+    if (task < n_pops) { pa = pb = task; kind = 0; }
+    else {
+        const int u = task - n_pops, k = u >> 1;
+        int x = 0, rem = k;
+        while (rem >= n_pops - 1 - x) { rem -= n_pops - 1 - x; ++x; }
+        const int y = x + 1 + rem;
+        const bool xf = pop_rank[x] < pop_rank[y];
+        pa = xf ? x : y;
+        pb = xf ? y : x;
+        kind = 1 + (u & 1);
+    }
+    const int as = pop_start[pa], na = pop_start[pa + 1] - as, bs = pop_start[pb], nb_ = pop_start[pb + 1] - bs;
+    const int nr = kind == 2 ? na + nb_ : na, nc = kind == 0 ? na : kind == 1 ? nb_ : na + nb_;
+    const int n = nr * nc;
+    const int32_t *Cw = Cmat + (size_t)win * cN * cN, *Dw = Dmat + (size_t)win * N * N;
+    const int thr = min_pair_sites > 1 ? min_pair_sites : 1;
+    unsigned long long valid = 0ull;
+    double acc = 0.0;                                        // (thread 0's: the pieces before this one)
+    for (int base = 0; base < n; base += PG_NP_PIECE) {
+        const int m = n - base < PG_NP_PIECE ? n - base : PG_NP_PIECE;
+        const int32_t *T = trees + (m == PG_NP_PIECE ? full_tree : task_tree[task]);
+        const int L = T[0], n_inner = T[1], n_levels = T[2];
+        const int tree_len = (L + 1) + 2 * n_inner + (n_levels + 1);
+        __syncthreads();                                     // the piece before is read out
+        for (int t = tid; t < tree_len; t += 256) tree_s[t] = T[3 + t];
+        __syncthreads();
+        const int32_t *leaf_off = tree_s, *node_l = leaf_off + L + 1, *node_r = node_l + n_inner, *level_start = node_r + n_inner;
+        for (int l0 = 0; l0 < L; l0 += PG_NP_STAGE_LEAVES) {
+            const int l1 = l0 + PG_NP_STAGE_LEAVES < L ? l0 + PG_NP_STAGE_LEAVES : L;
+            const int k0 = leaf_off[l0], k1 = leaf_off[l1];
+            {
+                const int k = k0 + tid;
+                int r = (base + k) / nc, cc = (base + k) - r * nc;
+                const int qi = 256 / nc, qj = 256 - qi * nc;
+                constexpr int U = PG_NP_STAGE_LEAVES * 128 / 256;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (k + 256 * u < k1) {
+                        const int i = ref_row[r < na ? as + r : bs + (r - na)];
+                        const int j = ref_row[kind == 1 ? bs + cc : (cc < na ? as + cc : bs + (cc - na))];
+                        double v = 0.0;
+                        if (i != j) {                                // (both triangles hold the counts: k_mirror_lower)
+                            const int c = Cw[(size_t)(i >> cshift) * cN + (j >> cshift)];
+                            if (c >= thr) {
+                                const double cd = (double)c;
+                                v = quot_counts((double)Dw[(size_t)i * N + j], cd, rcp_counts(cd));
+                                ++valid;
+                            }
+                        }
+                        q[k + 256 * u - k0] = v;
+                    }
+                    r += qi;
+                    cc += qj;
+                    if (cc >= nc) { cc -= nc; ++r; }
+                }
+            }
+            __syncthreads();
+            {
+                const int leaf = l0 + (tid >> 3), j = tid & 7;
+                if (leaf < l1) {                                     // (the eight lanes of a run share the condition)
+                    const int off = leaf_off[leaf] - k0, len = leaf_off[leaf + 1] - leaf_off[leaf];
+                    double res;
+                    if (len < 8) {
+                        res = 0.0;
+                        for (int i = 0; i < len; ++i) res = res + q[off + i];
+                    } else {
+                        const int m8 = len - (len & 7);
+                        double rj = q[off + j];
+                        for (int i = 8; i < m8; i += 8) rj = rj + q[off + i + j];
+                        rj = rj + __shfl_xor(rj, 1, 64);
+                        rj = rj + __shfl_xor(rj, 2, 64);
+                        rj = rj + __shfl_xor(rj, 4, 64);
+                        res = rj;
+                        for (int i = m8; i < len; ++i) res = res + q[off + i];
+                    }
+                    if (j == 0) slots[leaf] = res;
+                }
+            }
+            __syncthreads();
+        }
+        for (int lv = 0; lv < n_levels; ++lv) {
+            for (int idx = level_start[lv] + tid; idx < level_start[lv + 1]; idx += 256) slots[L + idx] = slots[node_l[idx]] + slots[node_r[idx]];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const double root = slots[n_inner > 0 ? L + n_inner - 1 : 0];
+            acc = base == 0 ? root : acc + root;
+        }
+    }
+    valid = pg_wave_sum(valid);
+    if ((tid & 63) == 0) shc[tid >> 6] = valid;
+    __syncthreads();
+    if (tid == 0) {
+        sum_out[(size_t)win * n_tasks + task] = 0.0 + acc;        // np.add.reduce starts from the identity
+        cnt_out[(size_t)win * n_tasks + task] = (int64_t)(shc[0] + shc[1] + shc[2] + shc[3]);
+    }
+}
+
 // pi / dxy / Fst from k_popdist_np's sums and counts (task order: pi of every population, then dxy and pi_t of every pair x < y,
 // x-major); the float64 operations of genomics.py:88-90 and 976-993 in the reference's order, the pair oriented by pop_rank
 __global__ __launch_bounds__(256) void k_popstats_np(const double *__restrict__ sums, const int64_t *__restrict__ cnts, int n_win,
@@ -853,9 +973,27 @@ void pg_launch_popdist_np(hipStream_t st, const int32_t *Cmat, const int32_t *Dm
                        n_pops, min_data, do_pairs, out, win_lo, win_hi, max_sites);
 }
 
+void pg_launch_popdist_np_big(hipStream_t st, const int32_t *Cmat, const int32_t *Dmat, int N, int cN, int cshift, int n_win,
+                              const int32_t *pop_start, int n_pops, const int32_t *ref_row, const int32_t *pop_rank,
+                              const int32_t *task_tree, const int32_t *trees, int full_tree, int min_pair_sites, double min_data,
+                              int do_pairs, double *sums, int64_t *cnts, double *out, const int64_t *win_lo, const int64_t *win_hi,
+                              long long max_sites) {
+    if (n_win <= 0 || n_pops <= 0) return;
+    const int ntD = (N + 31) / 32, ntC = (cN + 31) / 32;
+    hipLaunchKernelGGL(k_mirror_lower, dim3(ntD * (ntD + 1) / 2, n_win), dim3(256), 0, st, const_cast<int32_t *>(Dmat), N, win_lo, win_hi, max_sites);
+    hipLaunchKernelGGL(k_mirror_lower, dim3(ntC * (ntC + 1) / 2, n_win), dim3(256), 0, st, const_cast<int32_t *>(Cmat), cN, win_lo, win_hi, max_sites);
+    hipLaunchKernelGGL(k_popdist_np_big, dim3(n_pops * n_pops, n_win), dim3(256), 0, st, Cmat, Dmat, N, cN, cshift, pop_start, n_pops, ref_row,
+                       pop_rank, task_tree, trees, full_tree, min_pair_sites, sums, cnts, win_lo, win_hi, max_sites);
+    const long long total = (long long)n_win * (n_pops * (n_pops + 1) / 2);
+    hipLaunchKernelGGL(k_popstats_np, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, sums, cnts, n_win, pop_start, pop_rank,
+                       n_pops, min_data, do_pairs, out, win_lo, win_hi, max_sites);
+}
+
 // ------------------------------------------------------------------------------------------------------
-// K_indpair: one thread per unordered individual pair (s<=t); haplotype slots of an individual are contiguous.
+// K_indpair: one thread per unordered individual pair (s<=t); haplotype slots of an individual are contiguous.  BIG: some individual
+// has three haplotypes or more, so blocks of 8 values and more occur (their code stays out of the kernel of a haploid / diploid layout)
 // ------------------------------------------------------------------------------------------------------
+template <bool BIG>
 __global__ __launch_bounds__(256) void k_indpair_fin(const int32_t *__restrict__ Cmat, const int32_t *__restrict__ Dmat,
                                                      int N, int cN, int cshift, const int32_t *__restrict__ samp_start,
                                                      const int32_t *__restrict__ samp_rank, int n_samp,
@@ -884,6 +1022,30 @@ __global__ __launch_bounds__(256) void k_indpair_fin(const int32_t *__restrict__
         // order of the samples (distMat.py:44-45): samp_rank (pg_set_sample_rank; slot order until set)
         const int as = samp_start[s], ns = samp_start[s + 1] - as, bs = samp_start[t], nt = samp_start[t + 1] - bs;
         const bool s_rows = samp_rank[s] <= samp_rank[t];
+        if (BIG && mean_mode != 0 && ns * nt >= 8) {
+            // a block of 8 values and more (an individual of more than two haplotypes): np.nanmean adds the flattened block up in
+            // NumPy's pairwise order (pg_np_sum.h: eight strided partial sums combined as a tree, the tail one by one, halves beyond
+            // 128 values), a nan as 0.0 at its place.  Within an individual that is the whole symmetric block with its diagonal (nan, or
+            // under includeSameWithSame zeros that count): twice the triangle's sum is another sum.  The cells are walked from their
+            // indices, each asked for once
+            const int rb = s_rows ? as : bs, cb = s_rows ? bs : as, nc = s_rows ? nt : ns;
+            long long valid = 0;
+            auto cell = [&](int k) -> double {
+                const int r = k / nc, a = rb + r, b = cb + (k - r * nc);
+                if (a == b) {
+                    valid += mean_mode == 2;
+                    return 0.0;
+                }
+                const int i = a < b ? a : b, j = a < b ? b : a;      // (the upper triangles hold the counts)
+                const int c = Cw[(size_t)(i >> cshift) * cN + (j >> cshift)];
+                if (c < thr) return 0.0;
+                ++valid;
+                return (double)Dw[(size_t)i * N + j] / (double)c;
+            };
+            const double tot = np_pairwise_sum_of<3>(cell, 0, ns * nt);
+            sum_out[(size_t)win * npairs + pidx] = valid > 0 ? tot / (double)valid : __longlong_as_double(0x7ff8000000000000ll);
+            continue;
+        }
         for (int u = 0; u < ns * nt; ++u) {
             const int a = as + (s_rows ? u / nt : u % ns), b = bs + (s_rows ? u % nt : u / ns);
             if (s == t && a >= b) continue;
@@ -908,13 +1070,17 @@ __global__ __launch_bounds__(256) void k_indpair_fin(const int32_t *__restrict__
 
 void pg_launch_indpair_fin(hipStream_t st, const int32_t *Cmat, const int32_t *Dmat, int N, int cN, int cshift, int n_win,
                            const int32_t *samp_start, const int32_t *samp_rank, int n_samp, int min_pair_sites, double *sum_out,
-                           int64_t *cnt_out, int mean_mode) {
+                           int64_t *cnt_out, int mean_mode, int max_ploidy) {
     if (n_win <= 0 || n_samp <= 0) return;
     long long npairs = (long long)n_samp * (n_samp + 1) / 2;
     int bx = (int)((npairs + 255) / 256);
     if (bx > 2048) bx = 2048;
-    hipLaunchKernelGGL(k_indpair_fin, dim3(bx, n_win), dim3(256), 0, st, Cmat, Dmat, N, cN, cshift, samp_start, samp_rank, n_samp,
-                       min_pair_sites, sum_out, cnt_out, mean_mode);
+    if (max_ploidy >= 3)                                     // (3 x 3 = 9 values; up to two haplotypes each: at most 4)
+        hipLaunchKernelGGL(k_indpair_fin<true>, dim3(bx, n_win), dim3(256), 0, st, Cmat, Dmat, N, cN, cshift, samp_start, samp_rank, n_samp,
+                           min_pair_sites, sum_out, cnt_out, mean_mode);
+    else
+        hipLaunchKernelGGL(k_indpair_fin<false>, dim3(bx, n_win), dim3(256), 0, st, Cmat, Dmat, N, cN, cshift, samp_start, samp_rank, n_samp,
+                           min_pair_sites, sum_out, cnt_out, mean_mode);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -36,3 +36,28 @@ PG_NP_SUM_FN double np_pairwise_sum(const double *a, int n) {
     n2 -= n2 % 8;
     return np_pairwise_sum<(DEPTH > 0 ? DEPTH - 1 : 0)>(a, n2) + np_pairwise_sum<(DEPTH > 0 ? DEPTH - 1 : 0)>(a + n2, n - n2);
 }
+
+// The same order over values that are not stored: f(k) is element k of the flattened array, asked for exactly once (k_indpair_fin: the
+// cells of an individual pair's haplotype block, a nan of the block as the 0.0 np.nanmean adds in its place).  A 26 x 26 block has 676
+// values: DEPTH 3 holds up to 968.
+template <int DEPTH, class F>
+PG_NP_SUM_FN double np_pairwise_sum_of(F &f, int off, int n) {
+    if (n < 8) {
+        double r = 0.0;
+        for (int i = 0; i < n; ++i) r += f(off + i);
+        return r;
+    }
+    if (n <= 128 || DEPTH == 0) {
+        double r[8];
+        for (int j = 0; j < 8; ++j) r[j] = f(off + j);
+        int i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; ++j) r[j] += f(off + i + j);
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += f(off + i);
+        return res;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    return np_pairwise_sum_of<(DEPTH > 0 ? DEPTH - 1 : 0)>(f, off, n2) + np_pairwise_sum_of<(DEPTH > 0 ? DEPTH - 1 : 0)>(f, off + n2, n - n2);
+}

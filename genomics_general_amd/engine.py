@@ -169,8 +169,9 @@ class Engine:
         self._pair_first = "slot"
 
     def set_sum_order(self, mode):
-        """0: the float64 sums of pi / dxy / Fst and of the ABBA-BABA statistics in NumPy's order for windows of up to 256 sites (PG_NP_MAX_SITES);
-        1: for every window; 2: for none (pg_set_sum_order)"""
+        """0: the float64 sums of pi / dxy / Fst and of the ABBA-BABA statistics in NumPy's order for windows of up to 256 sites (PG_NP_MAX_SITES)
+        -- for pi / dxy / Fst where the layout fits k_popdist_np: at most 361 haplotypes in a block of two populations --;
+        1: for every window and every layout (k_popdist_np_big beyond 361); 2: for none (pg_set_sum_order)"""
         check(self._L.pg_set_sum_order(self._h, int(mode)))
 
     def set_pair_first(self, first):
@@ -786,7 +787,9 @@ class WindowBatch:
         """Alignment.indPairDists as one array [window][pair]: the nanmean of every individual pair's haplotype block, finished
         on the device (pg_indpairdist_mean).  Pair (s<=t) in slot order of the individuals sits at lay.sample_pair_index(s,t).
         As in the reference (which mutates its cached distance matrix), a preceding groupDistStats leaves its minSites mask
-        and nan diagonal in force."""
+        and nan diagonal in force.  A block is added up as np.nanmean adds it: row by row from 0.0 below 8 values, in NumPy's
+        pairwise order (eight strided partial sums combined as a tree, the tail one by one, halves beyond 128 values) from 8 values
+        on -- individuals of three haplotypes and more --, within an individual over the whole symmetric block."""
         lay = self.lay
         n = lay.n_samp
         npairs = n * (n + 1) // 2

@@ -307,19 +307,29 @@ def nanmean_min(a, minimum=0):
     return np.nanmean(a)
 
 
-def group_dist_stats(aln, D, C, do_pairs=True, min_sites=None, min_data=0.01):
-    """genomics.py:956-995 groupDistStats.  Returns (stats dict, masked distance matrix)."""
+def _block_sums(blk):
+    """(valid cells, size, math.fsum of the valid quotients: their exact sum, correctly rounded) of a block of the distance matrix"""
+    ok = ~np.isnan(blk)
+    return int(ok.sum()), int(blk.size), math.fsum(blk[ok].tolist())
+
+
+def group_dist_stats(aln, D, C, do_pairs=True, min_sites=None, min_data=0.01, with_sums=False):
+    """genomics.py:956-995 groupDistStats.  Returns (stats dict, masked distance matrix).
+    with_sums: a third value {"pi_x", "dxy_x_y", "pit_x_y" (x before y in np.unique's order): _block_sums of the block (x, x),
+    (x, y), (x + y, x + y)}: what a test needs to bound a sum formed in another order than NumPy's."""
     dm = dist_from_counts(D, C)
     if min_sites:
         dm[C < min_sites] = np.nan
     np.fill_diagonal(dm, np.nan)
     pops, inv = np.unique(np.array(aln.groups), return_inverse=True)
     idx = [list(np.where(inv == x)[0]) for x in range(len(pops))]
-    out = {}
+    out, sums = {}, {}
     for x in range(len(pops)):
         out["pi_" + pops[x]] = nanmean_min(dm[np.ix_(idx[x], idx[x])], min_data)
+        if with_sums:
+            sums["pi_" + pops[x]] = _block_sums(dm[np.ix_(idx[x], idx[x])])
     if len(pops) == 1 or not do_pairs:
-        return out, dm
+        return (out, dm, sums) if with_sums else (out, dm)
     for x in range(len(pops) - 1):
         for y in range(x + 1, len(pops)):
             dxy = nanmean_min(dm[np.ix_(idx[x], idx[y])], min_data)
@@ -332,7 +342,10 @@ def group_dist_stats(aln, D, C, do_pairs=True, min_sites=None, min_data=0.01):
             with np.errstate(divide="ignore", invalid="ignore"):
                 fst = 1 - np.float64(pi_s) / np.float64(pi_t)
             out["Fst_%s_%s" % (pops[x], pops[y])] = out["Fst_%s_%s" % (pops[y], pops[x])] = fst
-    return out, dm
+            if with_sums:
+                sums["dxy_%s_%s" % (pops[x], pops[y])] = _block_sums(dm[np.ix_(idx[x], idx[y])])
+                sums["pit_%s_%s" % (pops[x], pops[y])] = _block_sums(dm[np.ix_(both, both)])
+    return (out, dm, sums) if with_sums else (out, dm)
 
 
 def ind_pair_dists(aln, dm, include_same=False):

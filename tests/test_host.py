@@ -682,7 +682,8 @@ def test_the_one_lane_numpy_sum_adds_up_like_numpy_as_a_program_of_its_own(tmp_p
     """tests/np_sum_main.cpp: csrc/pg_np_sum.h's np_pairwise_sum -- what k_hapstats sums f^2 with (depth 9, and the view behind the
     first cluster for H2) and k_paint a population's distances (depth 6) -- as host code under AddressSanitizer and
     UndefinedBehaviorSanitizer, against np.sum to the last bit: every length 0 .. 300 and the lengths around 512, 1024, 2048, 4096 and
-    8192 (above 2048, k_paint's limit, for depth 9 only).  The values are signed with magnitudes spread log-uniformly over 1e-8 .. 1e8,
+    8192 (above 2048, k_paint's limit, for depth 9 only); and np_pairwise_sum_of, the same order over values a function hands out
+    (k_indpair_fin's haplotype blocks: depth 3, up to 968 values), which must ask for every element once.  The values are signed with magnitudes spread log-uniformly over 1e-8 .. 1e8,
     so that the order of the additions shows: a left-to-right sum of the same values must differ from np.sum at three quarters of
     the lengths from 16 on (it does at about 85 %)"""
     import struct
@@ -692,7 +693,7 @@ def test_the_one_lane_numpy_sum_adds_up_like_numpy_as_a_program_of_its_own(tmp_p
                            "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "np_sum_main.cpp"),
                            "-o", exe])
     rng = np.random.default_rng(20261)
-    lengths = list(range(301)) + [n + d for n in (512, 1024, 2048, 4096, 8192) for d in (-1, 0, 1)]
+    lengths = list(range(301)) + [n + d for n in (512, 1024, 2048, 4096, 8192) for d in (-1, 0, 1)] + [676, 968]      # (26 x 26; depth 3's last)
     arrays = [rng.choice([-1.0, 1.0], size=n) * 10.0 ** rng.uniform(-8.0, 8.0, size=n) for n in lengths]
     src, dst = str(tmp_path / "arrays.bin"), str(tmp_path / "sums.txt")
     with open(src, "wb") as f:
@@ -710,10 +711,11 @@ def test_the_one_lane_numpy_sum_adds_up_like_numpy_as_a_program_of_its_own(tmp_p
         return int(np.float64(v).view(np.uint64))
 
     differ = counted = 0
-    for a, (s6, s9, tail) in zip(arrays, got):
+    for a, (s6, s9, tail, of) in zip(arrays, got):
         n = len(a)
         want = np.sum(a) if n else np.float64(0.0)
         assert s9 == bits(want), (n, "depth 9")
+        assert of == bits(want), (n, "values handed out by a function (k_indpair_fin: depth 3 up to 968 values)")
         if n <= 2048:
             assert s6 == bits(want), (n, "depth 6")
         assert tail == bits(a[1:].sum() if n > 1 else 0.0), (n, "the view behind the first value")
@@ -724,7 +726,7 @@ def test_the_one_lane_numpy_sum_adds_up_like_numpy_as_a_program_of_its_own(tmp_p
                 left += x
             differ += bits(left) != bits(want)
     print("left-to-right differs from np.sum at %d of %d lengths >= 16" % (differ, counted))
-    assert counted == 300 and 4 * differ >= 3 * counted, (differ, counted)
+    assert counted == 302 and 4 * differ >= 3 * counted, (differ, counted)
 
 
 # ---- the device tokenizer's case table (tests/tok_cases.py) and its route plan (csrc/pg_tok_plan.h), without a GPU ----------------------
