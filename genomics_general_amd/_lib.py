@@ -265,6 +265,26 @@ SIGNATURES = {
     "pg_sfs_end": (C.c_int, [_P]),
     "pg_sfs_target_base": (C.c_int, [_i64p, C.c_void_p, C.POINTER(C.c_int)]),
     "pg_sfs_time_site_counts": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_double)]),
+    "pg_ws_text": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                             C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_ws_stats_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "pg_ws_reserve": (C.c_int, [_P, C.c_int, C.c_int64]),
+    "pg_ws_put": (C.c_int, [_P, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    "pg_ws_stats": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.POINTER(C.c_double)]),
+    "pg_ws_copy_time": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "pg_ws_end": (C.c_int, [_P]),
+    "pg_ws_dev_config": (C.c_int, [_P, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "pg_ws_dev_submit": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_int64]),
+    "pg_ws_dev_submit_bgzf": (C.c_int, [_P, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_char_p, C.c_int64, C.c_int64]),
+    "pg_ws_dev_parse": (C.c_int, [_P, C.c_int, C.c_int64, C.POINTER(C.c_int64)]),
+    "pg_ws_dev_collect": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pg_ws_dev_meta": (C.c_int, [_P, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_ws_dev_text": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "pg_ws_dev_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pg_kernel_time": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "pg_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "pg_host_free": (C.c_int, [C.c_void_p]),

@@ -2093,3 +2093,14 @@ def seqtogeno_main(argv=None):
     k_s2g_gather and transposed back into site lines by k_s2g_tile"""
     from . import seqgeno
     return seqgeno.main(argv)
+
+
+# ==========================================================================================================
+# windowStats.py  (SURVEY.md section 2 row 13: per-window statistics of a table's columns; genomics_general_amd/wstats.py)
+# ==========================================================================================================
+@guarded_main
+def windowstats_main(argv=None):
+    """Drop-in for the reference's windowStats.py (windowStats.py:24-190): the selected columns are held on the device and every
+    window's mean, median, min, max, sd, sum and quantiles are computed there by k_ws_stats"""
+    from . import wstats
+    return wstats.main(argv)

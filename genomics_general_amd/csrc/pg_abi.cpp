@@ -160,6 +160,7 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
     pg_comm_destroy(c);
     (void)pg_sfs_end(c);
     (void)pg_merge_dev_end(c);
+    (void)pg_ws_end(c);
     c->paint.release();
     for (int k = 0; k < 2; ++k) {
         c->slot[k].Vp.release();
@@ -229,6 +230,13 @@ extern "C" int pg_ctx_destroy(pg_ctx *c) {
         pg_ctx::EigDev::Slot &E = c->eig.s[k];
         E.snp.release(); E.geno.release(); E.site.release(); E.rlen.release(); E.entry.release(); E.roff.release(); E.rank.release(); E.status.release(); E.h_status.release();
         if (E.done) (void)hipEventDestroy(E.done);
+    }
+    c->wsl.sel_field.release();
+    for (int k = 0; k < 2; ++k) {
+        pg_ctx::WsLines::Slot &W = c->wsl.s[k];
+        W.rlen.release(); W.roff.release(); W.rank.release(); W.pos.release(); W.soff.release(); W.slen.release(); W.runf.release();
+        W.status.release(); W.h_status.release();
+        if (W.done) (void)hipEventDestroy(W.done);
     }
     c->seq.sel_col.release(); c->seq.sel_off.release(); c->seq.sel_len.release();
     for (int k = 0; k < 2; ++k) {

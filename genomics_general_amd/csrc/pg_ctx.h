@@ -250,6 +250,19 @@ struct pg_ctx {
             int64_t snp_cap = 0, first_site = 0;
         } s[2];
     } eig;
+    // a table's lines parsed into the value store on the device (pg_ws_dev.hip: k_ws_lines): the header's field count, the selected
+    // fields and, per text slot, the lines' site flags, their ranks, and the sites' positions, scaffold places and run flags
+    struct WsLines : PgLineRoute {
+        int n_fields = 0, n_sel = 0;
+        DevBuf<int32_t> sel_field;
+        struct Slot : LineSlot {
+            DevBuf<uint32_t> rlen;
+            DevBuf<int64_t> roff, rank, pos, soff;
+            DevBuf<int32_t> slen;
+            DevBuf<uint8_t> runf;
+            int64_t base = 0;
+        } s[2];
+    } wsl;
     // .geno lines turned into sequences on the device (pg_seq_dev.hip): the option set, the selection tables and, per text slot of the
     // tokenizer, the lines' records, the kept lines' places, the sites' records and the matrix [n_seq][pitch]
     struct SeqDev : PgLineRoute {
@@ -337,6 +350,7 @@ struct pg_ctx {
     } paint;
     void *sfs = nullptr;           // pg_sfs_begin .. pg_sfs_end: the spectra's tables and staging (pg_sfs.hip owns the type)
     void *merge = nullptr;         // pg_merge_dev_config .. pg_merge_dev_end: the files' text regions, keys and the round's output (pg_merge_dev.hip owns the type)
+    void *ws = nullptr;            // pg_ws_reserve .. pg_ws_end: windowStats.py's value store, window table and results (pg_ws_dev.hip owns the type)
     // pi / dxy / Fst in NumPy's summation order (k_popdist_np): the reference's row order within the populations and the rank of
     // the population names (pg_set_reference_order; identity until set), the pairwise-summation trees of the block lengths
     DevBuf<int32_t> ref_row, pop_rank, np_trees, np_task_tree;

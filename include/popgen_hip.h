@@ -573,6 +573,54 @@ int pg_paint(pg_ctx *ctx, const int64_t *win_lo, const int64_t *win_hi, int n_wi
              const int32_t *ref_start, const int32_t *ref_slot, int min_sites, int mode, const int64_t *crit, double delta, int noresult,
              int32_t *decision_out, int64_t *n_flagged_out, int64_t *flag_cell_out, double *flag_means_out);
 
+/* ---- per-window column statistics (the windowStats.py drop-in, genomics_general_amd/wstats.py) --------------------------------------
+ * Replaces windowStats.py:160-182: per window and column, over the non-nan values in file order, mean / median / min / max / sd /
+ * sum / q5 q10 q25 q75 q90 q95 (statistic s = bit s of `mask`, in this order) as NumPy 2.2 computes them, to the last bit.
+ * Host (pg_ws.cpp, no context): pg_ws_text parses a block of lines -- sel_col[k] the value field of selected column k, n_names the
+ * header's value names (exact: a line must hold exactly that many) -- into vals[n_sel][pitch], pos, the scaffolds' places in the text
+ * and new_run; cells of another spelling than pg_ws_core.h's regular one are listed in irr[.][4] = site, selected column (-1: the
+ * position), offset, length (*n_irr_out may exceed cap_irr; *n_sites_out > cap_sites: nothing was written, come again with more room).
+ * *err_out: 0, or 1 a line too short, 2 a line too long (exact), 7 not ASCII, at line *err_line_out; the sites in front of it stand.
+ * pg_ws_stats_host: windows [lo, hi) of sites -> out[n_win][n_cols][12], cnt[n_win][n_cols] non-nan values, flag[n_win][n_cols] = 1
+ * where min / max were asked of no value.
+ * Device (pg_ws_dev.hip): pg_ws_reserve reserves the value store [n_cols][n_sites] (held against the scratch budget: PG_ERR_ARG with the
+ * knob's name), pg_ws_put uploads sites [site0, site0 + n) of a column, pg_ws_stats runs k_ws_stats over the windows -- a
+ * workgroup per window and column; up to lds_vals (0: the default, PG_WS_LDS_DEFAULT; 8192 at most) values are sorted in LDS, more
+ * go through a radix select over global memory -- and tier_out[2] (may be NULL) counts the cells of either tier; pg_ws_copy_time
+ * copies the store device to device once (the kernels' floor, tools/wstats_bench.py); pg_ws_end frees (pg_ctx_destroy ends an open one). */
+#define PG_WS_LDS_DEFAULT 8192
+int pg_ws_text(const char *text, int64_t len, int n_sel, const int32_t *sel_col, int n_names, int exact, int n_threads, int64_t cap_sites,
+               double *vals, int64_t pitch, int64_t *pos, int64_t *scaf_off, int32_t *scaf_len, uint8_t *new_run, int64_t cap_irr,
+               int64_t *irr, int64_t *n_sites_out, int64_t *n_irr_out, int64_t *n_lines_out, int *err_out, int64_t *err_line_out,
+               int64_t *err_site_out);
+int pg_ws_stats_host(const double *vals, int64_t pitch, int n_cols, const int64_t *lo, const int64_t *hi, int64_t n_win, uint32_t mask,
+                     int n_threads, double *out, int64_t *cnt, uint8_t *flag);
+int pg_ws_reserve(pg_ctx *ctx, int n_cols, int64_t n_sites);
+int pg_ws_put(pg_ctx *ctx, int col, int64_t site0, const double *vals, int64_t n);
+int pg_ws_stats(pg_ctx *ctx, const int64_t *lo, const int64_t *hi, int64_t n_win, uint32_t mask, int lds_vals, double *out, int64_t *cnt,
+                uint8_t *flag, int64_t *tier_out, double *ms_out);
+int pg_ws_copy_time(pg_ctx *ctx, double *ms_out);
+/* The lines parsed on the device (k_ws_lines), a block of whole lines through text slot 0 or 1 (csrc/pg_line_slot.h: submit, parse,
+ * collect).  pg_ws_dev_config: n_fields the header's fields, sel_field[n_sel] the field (>= 2) of every selected column; *taken_out = 0:
+ * the host route parses.  pg_ws_dev_submit / _submit_bgzf: the text, or bgzip members that k_inflate inflates into the slot.
+ * pg_ws_dev_parse: base = the sites the store holds (pg_ws_reserve(ctx, n_sel, base) first); the store grows for the block's lines and
+ * the kernels are queued.  pg_ws_dev_collect: *host_line_out < 0: *n_sites_out sites stand behind base (pg_ws_reserve(ctx, n_sel, base +
+ * n) takes them in), pg_ws_dev_meta gives their positions, run flags (another scaffold than the site before; the block's first site: 1)
+ * and the scaffolds' places in the block's text (pg_ws_dev_text); else the block is the host route's (a line of another field count than
+ * the header's, a cell outside the regular spelling, a position that is not 1 .. 18 digits, a byte that is not ASCII, a carriage
+ * return, a blank line, no final line feed) and is counted in pg_ws_dev_stats' host blocks. */
+int pg_ws_dev_config(pg_ctx *ctx, int n_fields, int n_sel, const int32_t *sel_field, int *taken_out);
+int pg_ws_dev_submit(pg_ctx *ctx, int slot, const char *text, int64_t len);
+int pg_ws_dev_submit_bgzf(pg_ctx *ctx, int slot, const uint8_t *comp, int64_t comp_len, const uint32_t *in_off, const uint32_t *in_len,
+                          const uint32_t *out_len, const uint32_t *crc, int64_t n_members, const char *head, int64_t head_len,
+                          int64_t text_len);
+int pg_ws_dev_parse(pg_ctx *ctx, int slot, int64_t base, int64_t *n_lines_out);
+int pg_ws_dev_collect(pg_ctx *ctx, int slot, int64_t *n_sites_out, int64_t *host_line_out, int64_t *n_lines_out);
+int pg_ws_dev_meta(pg_ctx *ctx, int slot, int64_t n, int64_t *pos, uint8_t *runf, int64_t *soff, int32_t *slen);
+int pg_ws_dev_text(pg_ctx *ctx, int slot, int64_t off, int64_t len, uint8_t *dst);
+int pg_ws_dev_stats(pg_ctx *ctx, int64_t *blocks_out, int64_t *host_blocks_out);
+int pg_ws_end(pg_ctx *ctx);
+
 /* ---- per-haplotype called-site counts ------------------------------------------------------------ */
 /* Replaces Alignment.seqNonNan (genomics.py:1038-1040) as used by distMat.py:40 (--minPerInd):
  * called_out[n_win][n_hap] = number of sites of the window at which the haplotype slot is called. */
