@@ -78,6 +78,9 @@ extern "C" void *pgm_emul_config(const pg_merge_cfg *cfg, const char *sep, const
 
 extern "C" void pgm_emul_free(void *e) { delete static_cast<Emul *>(e); }
 
+// pgm_hash itself: tests/merge_edge_cases.py searches name sets with a port of it
+extern "C" uint32_t pgm_emul_hash(const uint8_t *s, int64_t len) { return pgm_hash(s, len); }
+
 // a block behind what the rounds before left of file f (take_block)
 extern "C" int pgm_emul_submit(void *e, int f, const char *text, int64_t len) {
     Emul &E = *static_cast<Emul *>(e);
